@@ -13,8 +13,9 @@ into a VariantDB.
 
 Order of a run: upload (outside the timed region), `--settle` untimed steps (default 300: a device fresh from boot was seen to run its
 first seconds of steps 7 % slower than ever after, with the kernels' own durations unchanged), `--warmup` untimed steps, barrier +
-synchronize, EXACTLY `--steps` timed steps, barrier + synchronize; then, untimed, the kernel durations on launches that have the GPU to
-themselves (roofline), the PCIe-inclusive loop, the CPU baseline, the native BAM -> VCF run and the side configurations.
+synchronize, EXACTLY `--steps` timed steps, barrier + synchronize; `--dump-outputs DIR`: the results of the last timed step as .npy files.
+With `--full` then, untimed, the kernel durations on launches that have the GPU to themselves (roofline), the PCIe-inclusive loop, the
+CPU baseline, the native BAM -> VCF run and the side configurations; without it the run ends with the headline.
 
 Prints ONE JSON line on rank 0."""
 import argparse
@@ -248,6 +249,46 @@ def bam_e2e(d: str, region_args, gen_args, what: str, extra=("--devices", "0,0",
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+STAT_KEYS = ("status", "final_k", "n_builds", "n_variants", "n_kmers", "max_nodes", "sum_nodes")
+
+
+def dump_outputs(d: str, variants, stats, linked: bool) -> None:
+    """--dump-outputs: what Engine.results() handed over after the last timed step, as float64 arrays (every value is an integer below
+    2**53: exact) and float32 bytes.
+      variants.npy        one row per record: window, seq, chr_id, pos, code, prev_bp_ref, prev_bp_alt, kmer, cov[8], len(ref), len(alt), len(str)
+      variant_bases.npy   the bytes of ref + alt + str of every record, one record after the other
+      window_stats.npy    one row per window: STAT_KEYS
+      --linked also: variant_hp.npy (12 counts per record), variant_bx_len.npy (the sizes of the 4 barcode sets per record),
+                     variant_bx.npy (the barcode ranks of those sets, one after the other)
+    Over DUMP_LIMIT_BYTES in all, a fixed (seeded) sample of the windows and of the records is written, in order, and
+    window_rows.npy / variant_rows.npy say which rows were kept."""
+    import numpy as np
+    cap_w, cap_v = len(stats), len(variants)
+    while True:
+        rows = {}
+        for name, n, cap in (("window_rows", len(stats), cap_w), ("variant_rows", len(variants), cap_v)):
+            if n > cap:
+                rows[name] = np.sort(np.random.default_rng(22).choice(n, size=cap, replace=False))
+        vs = [variants[i] for i in rows["variant_rows"]] if "variant_rows" in rows else variants
+        ws = [stats[i] for i in rows["window_rows"]] if "window_rows" in rows else stats
+        out = {"variants": np.array([[v["window"], v["seq"], v["chr_id"], v["pos"], ord(v["code"]), ord(v["prev_bp_ref"]), ord(v["prev_bp_alt"]),
+                                      v["kmer"], *v["cov"], len(v["ref"]), len(v["alt"]), len(v["str"])] for v in vs], dtype=np.float64).reshape(-1, 19),
+               "variant_bases": np.frombuffer("".join(v["ref"] + v["alt"] + v["str"] for v in vs).encode(), dtype=np.uint8).astype(np.float32),
+               "window_stats": np.array([[s[k] for k in STAT_KEYS] for s in ws], dtype=np.float64).reshape(-1, len(STAT_KEYS))}
+        if linked:
+            out["variant_hp"] = np.array([v["hp"] for v in vs], dtype=np.float64).reshape(-1, 12)
+            out["variant_bx_len"] = np.array([[len(b) for b in v["bx"]] for v in vs], dtype=np.float64).reshape(-1, 4)
+            out["variant_bx"] = np.array([x for v in vs for b in v["bx"] for x in b], dtype=np.float64)
+        out.update({k: r.astype(np.float64) for k, r in rows.items()})
+        if sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES:
+            break
+        cap_w, cap_v = max(1, min(cap_w, len(ws)) // 2), max(1, min(cap_v, len(vs)) // 2)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,7 +310,14 @@ def main():
     ap.add_argument("--chain", type=int, default=1, help="1: a batch's kernels start when those of the batch before it (other engine) are through -- back to back, no host gap; 0: as soon as submitted")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every rank assembles its own contig of --windows windows; strong: ONE contig of --windows windows dealt out over the ranks in chunks (dist.shard_windows)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure the rest: roofline (kernel durations on launches of their own, PMC traffic record), the PCIe-inclusive "
+                         "loop, the CPU baseline, the native BAM -> VCF runs and the side configurations (--cpu-sample, --no-bam and --no-configs trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: its variant records and window stats, Engine.results()) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     maybe_spawn(sys.argv[1:], args.gpus)
 
     import numpy as np
@@ -488,18 +536,12 @@ def main():
             step_summary["kernel_ms_in_the_pipeline"] = [round(float(np.mean([k[i] for k in kl])), 3) for i in range(len(kl[0]))]
     if os.environ.get("LANCET_BENCH_STEPS"):
         print("[bench] step ms:", [round(x, 1) for x in step_ms], file=sys.stderr)
-    # kernel durations for the roofline: launches that have the GPU to themselves (with two batches in flight the HIP events of a
-    # kernel also cover the time it shares the device with the other batch's kernels)
-    kernel_ms = []
-    for _ in range(2):
-        eng.run()
-        kernel_ms.append(eng.kernel_times())
-
-    variants, stats = eng.results()
+    # what the last timed step computed, as a caller of Engine receives it (an engine's results stay valid until its next submit)
+    variants, stats = engs[(args.steps - 1) % nfl].results()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, variants, stats, args.linked)
     n_kmers = int(sum(s["n_kmers"] for s in stats))
     n_bad = sum(1 for s in stats if s["status"] < 0)
-    alg_bytes = workload.algorithmic_bytes(batch, stats, len(variants))
-    alg_build, alg_window = workload.algorithmic_bytes_split(batch, stats, len(variants))
     if world > 1:
         t = torch.tensor([n_kmers, n_bad], dtype=torch.int64, device=comm_device)
         dist.all_reduce(t)
@@ -507,47 +549,52 @@ def main():
     else:
         n_kmers_all, n_bad_all = n_kmers, n_bad
 
-    # PCIe-inclusive rate (never `value`): the batch handed over as host buffers every step; upload + trim/pack of one batch overlap
-    # the kernels of the previous one when two engines take turns
-    # (steady state: the clock runs from the completion of the second step to that of the last -- the first upload has no kernels to hide
-    #  behind and the last kernels no upload to hide)
-    pend = []
-    ne2e = 10
-    done_at = []
-    tl = []
-    for i in range(ne2e):
-        e = engs[i % nfl]
-        ta = time.perf_counter()
-        e.upload(batch)
-        tb = time.perf_counter()
-        e.submit(after=pend[-1] if pend and args.chain else None)
-        tc = time.perf_counter()
-        pend.append(e)
-        if len(pend) >= nfl:
+    if args.full:
+        # kernel durations for the roofline: launches that have the GPU to themselves (with two batches in flight the HIP events of a
+        # kernel also cover the time it shares the device with the other batch's kernels)
+        kernel_ms = []
+        for _ in range(2):
+            eng.run()
+            kernel_ms.append(eng.kernel_times())
+        alg_bytes = workload.algorithmic_bytes(batch, stats, len(variants))
+        alg_build, alg_window = workload.algorithmic_bytes_split(batch, stats, len(variants))
+
+        # PCIe-inclusive rate (never `value`): the batch handed over as host buffers every step; upload + trim/pack of one batch overlap
+        # the kernels of the previous one when two engines take turns
+        # (steady state: the clock runs from the completion of the second step to that of the last -- the first upload has no kernels to hide
+        #  behind and the last kernels no upload to hide)
+        pend = []
+        ne2e = 10
+        done_at = []
+        tl = []
+        for i in range(ne2e):
+            e = engs[i % nfl]
+            ta = time.perf_counter()
+            e.upload(batch)
+            tb = time.perf_counter()
+            e.submit(after=pend[-1] if pend and args.chain else None)
+            tc = time.perf_counter()
+            pend.append(e)
+            if len(pend) >= nfl:
+                pend.pop(0).wait()
+                done_at.append(time.perf_counter())
+            tl.append((ta, tb, tc, time.perf_counter()))
+        while pend:
             pend.pop(0).wait()
             done_at.append(time.perf_counter())
-        tl.append((ta, tb, tc, time.perf_counter()))
-    while pend:
-        pend.pop(0).wait()
-        done_at.append(time.perf_counter())
-    e2e_s = (done_at[-1] - done_at[1]) / (ne2e - 2)
-    if os.environ.get("LANCET_BENCH_TIMELINE"):
-        z = tl[0][0]
-        for i, (ta, tb, tc, td) in enumerate(tl):
-            print(f"[e2e] step {i}: upload {1e3 * (ta - z):7.1f} .. {1e3 * (tb - z):7.1f}  submit .. {1e3 * (tc - z):7.1f}  wait .. {1e3 * (td - z):7.1f}", file=sys.stderr)
-        print("[e2e] completions", [round(1e3 * (x - z), 1) for x in done_at], file=sys.stderr)
-    t1 = time.perf_counter()
-    eng.upload(batch)
-    up_ms = 1000.0 * (time.perf_counter() - t1)
+        e2e_s = (done_at[-1] - done_at[1]) / (ne2e - 2)
+        if os.environ.get("LANCET_BENCH_TIMELINE"):
+            z = tl[0][0]
+            for i, (ta, tb, tc, td) in enumerate(tl):
+                print(f"[e2e] step {i}: upload {1e3 * (ta - z):7.1f} .. {1e3 * (tb - z):7.1f}  submit .. {1e3 * (tc - z):7.1f}  wait .. {1e3 * (td - z):7.1f}", file=sys.stderr)
+            print("[e2e] completions", [round(1e3 * (x - z), 1) for x in done_at], file=sys.stderr)
+        t1 = time.perf_counter()
+        eng.upload(batch)
+        up_ms = 1000.0 * (time.perf_counter() - t1)
 
     if rank == 0:
-        names = eng.kernel_names()
-        per_kernel = {nm: round(float(np.mean([k[i] for k in kernel_ms])), 3) for i, nm in enumerate(names)}
-        ms_all = float(sum(per_kernel.values()))
-        achieved = alg_bytes / (ms_all * 1e-3) / 1e9
-        own = [v for v in variants]
         h = hashlib.sha256()
-        for v in own:
+        for v in variants:
             h.update(repr((v["window"], v["seq"], v["pos"], v["code"], v["ref"], v["alt"], v["cov"], v["kmer"], v["str"])).encode())
         out = {
             "metric": "assembled windows/sec (whole node), 600bp windows, self-tuning k, synthetic T/N",
@@ -559,27 +606,34 @@ def main():
             "dtype": "u64", "data": "synthetic",
             "mkmers_per_s": round(n_kmers_all * args.steps / dt / 1e6, 2),
             "overflowed_windows": n_bad_all,
-            "value_e2e": round(n_local / e2e_s, 2),
-            "value_e2e_note": f"PCIe-inclusive, per GPU: host buffers -> upload + trim/pack ({up_ms:.0f} ms per batch) + kernels, {nfl} batch(es) in flight; never `value`",
+            **({"value_e2e": round(n_local / e2e_s, 2),
+                "value_e2e_note": f"PCIe-inclusive, per GPU: host buffers -> upload + trim/pack ({up_ms:.0f} ms per batch) + kernels, {nfl} batch(es) in flight; never `value`"}
+               if args.full else {}),
             "config": {"workload": f"chr22-scan proxy: {args.windows} windows/GPU x 600 bp, stride 100, "
                                    f"{args.cov:g}x tumor / {cov_n:g}x normal, 2x150 bp, k=11..101, active-region-off"
                                    + (f", {100 * args.str_fraction:g} % STR / {100 * args.lowcomplex_fraction:g} % low complexity" if args.str_fraction or args.lowcomplex_fraction else "")
                                    + (", --linked-reads (BX / HP tags)" if args.linked else ""),
                        "windows_per_gpu": args.windows, "coverage": [args.cov, cov_n], "reads_per_gpu": int(batch.n_reads),
                        "records_rank0_contig": len(variants), "records_sha256_rank0_contig": h.hexdigest()[:16],
-                       "slots_in_flight": n_slots, "batches_in_flight": nfl, "step_ms": step_summary, "settle": settle, "upload_first_ms": round(upload_first_ms, 1), "upload_ms": round(up_ms, 1),
+                       "slots_in_flight": n_slots, "batches_in_flight": nfl, "step_ms": step_summary, "settle": settle, "upload_first_ms": round(upload_first_ms, 1),
+                       **({"upload_ms": round(up_ms, 1)} if args.full else {}),
                        "windows_first_graph_in_lds": eng.prebuilt_count(), "graphs_built_ahead": eng.ahead_counts()[0], "graphs_taken_from_pool": eng.ahead_counts()[1],
                        "build_service": dict(zip(("posted", "served", "not_buildable", "taken_back"), eng.svc_counts())),
-                       "windows_rerun_worst_case_tier": eng.rerun_count(), "workspace_MB_per_slot": round(slot_bytes / 2 ** 20, 1),
-                       "kernel_ms": per_kernel},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
-                         "frac": round(achieved / 8000.0, 6), "traffic": None,
-                         "kernel": "+".join(names), "kernel_ms": round(ms_all, 3), "algorithmic_bytes_per_launch": int(alg_bytes),
-                         "per_kernel_ms": per_kernel, "per_kernel": kernel_rooflines(alg_build, alg_window, per_kernel),
-                         "note": "one pass over the batch = the listed kernels back to back on one stream; achieved = algorithmic bytes of the batch / the sum of their HIP-event durations, measured on launches that have the GPU to themselves (profiles/: rocprofv3 of `bench.py --in-flight 1`)",
-                         "pipelined": {"ms_per_step": round(1000.0 * dt / args.steps, 3), "achieved": round(alg_bytes / (dt / args.steps) / 1e9, 3), "frac": round(alg_bytes / (dt / args.steps) / 1e9 / 8000.0, 6)},
-                         "peak_measured_copy": 6290.0, "frac_of_measured_copy": round(achieved / 6290.0, 6)},
+                       "windows_rerun_worst_case_tier": eng.rerun_count(), "workspace_MB_per_slot": round(slot_bytes / 2 ** 20, 1)},
         }
+        if args.full:
+            names = eng.kernel_names()
+            per_kernel = {nm: round(float(np.mean([k[i] for k in kernel_ms])), 3) for i, nm in enumerate(names)}
+            ms_all = float(sum(per_kernel.values()))
+            achieved = alg_bytes / (ms_all * 1e-3) / 1e9
+            out["config"]["kernel_ms"] = per_kernel
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
+                               "frac": round(achieved / 8000.0, 6), "traffic": None,
+                               "kernel": "+".join(names), "kernel_ms": round(ms_all, 3), "algorithmic_bytes_per_launch": int(alg_bytes),
+                               "per_kernel_ms": per_kernel, "per_kernel": kernel_rooflines(alg_build, alg_window, per_kernel),
+                               "note": "one pass over the batch = the listed kernels back to back on one stream; achieved = algorithmic bytes of the batch / the sum of their HIP-event durations, measured on launches that have the GPU to themselves (profiles/: rocprofv3 of `bench.py --in-flight 1`)",
+                               "pipelined": {"ms_per_step": round(1000.0 * dt / args.steps, 3), "achieved": round(alg_bytes / (dt / args.steps) / 1e9, 3), "frac": round(alg_bytes / (dt / args.steps) / 1e9 / 8000.0, 6)},
+                               "peak_measured_copy": 6290.0, "frac_of_measured_copy": round(achieved / 6290.0, 6)}
         if world > 1:
             out["config"]["merged_records_vdb"] = last.get("n", 0)
             out["config"]["vdb_variants"] = last["db"].size() if "db" in last else 0
@@ -593,35 +647,36 @@ def main():
             out["windows_per_rank"] = n_local
             if one_gpu:
                 out["config"]["comm"] = "LANCET_BENCH_ONE_GPU=1: all ranks on device 0, gather over gloo -- a check of the N-rank path, not a measurement"
-        # HBM-side bytes per launch from the committed PMC passes (tools/pmc_total.sh -> profiles/r6_traffic.json): rocprofv3 cannot run
-        # inside this process, so the figure is looked up for the exact workload it was taken on -- and only when it was taken on THESE
-        # kernels (sha1 over lancet_amd/csrc/*.h, *.hip, recorded with the passes): a record of other kernels is not quoted.
-        try:
-            fp = workload.kernel_fingerprint()
-            for name in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json"):
-                tj = os.path.join(ROOT, "profiles", name)
-                if os.path.exists(tj):
-                    break
-            with open(tj) as fh:
-                for rec in json.load(fh)["measurements"]:
-                    if rec["windows"] == args.windows and rec["coverage"] == args.cov and rec.get("coverage_normal", rec["coverage"]) == cov_n \
-                            and rec.get("str_fraction", 0.0) == args.str_fraction and bool(rec.get("linked", False)) == bool(args.linked) and world == 1:
-                        if rec.get("kernel_fingerprint") != fp:
-                            out["roofline"]["traffic_note"] = (f"profiles/{name} holds PMC passes for this workload, but taken on other kernels (fingerprint "
-                                                               f"{rec.get('kernel_fingerprint')}, these are {fp}): not quoted; re-run tools/profile_round6.sh")
-                            break
-                        out["roofline"]["traffic"] = int((rec["FETCH_SIZE_KB"] / rec.get("fetch_calibration", 1.0) + rec["WRITE_SIZE_KB"]) * 1024)
-                        out["roofline"]["traffic_fetch_write"] = [int(rec["FETCH_SIZE_KB"] * 1024), int(rec["WRITE_SIZE_KB"] * 1024)]
-                        out["roofline"]["traffic_note"] = rec["note"]
-                        out["roofline"]["traffic_kernel_fingerprint"] = fp
+        if args.full:
+            # HBM-side bytes per launch from the committed PMC passes (tools/pmc_total.sh -> profiles/r6_traffic.json): rocprofv3 cannot run
+            # inside this process, so the figure is looked up for the exact workload it was taken on -- and only when it was taken on THESE
+            # kernels (sha1 over lancet_amd/csrc/*.h, *.hip, recorded with the passes): a record of other kernels is not quoted.
+            try:
+                fp = workload.kernel_fingerprint()
+                for name in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json"):
+                    tj = os.path.join(ROOT, "profiles", name)
+                    if os.path.exists(tj):
                         break
-        except (OSError, KeyError, ValueError):
-            pass
-        if args.cpu_sample and world == 1:
-            out["cpu_baseline"] = cpu_baseline(batch, params, variants, args.cpu_sample, args.cpu_sample_all)
+                with open(tj) as fh:
+                    for rec in json.load(fh)["measurements"]:
+                        if rec["windows"] == args.windows and rec["coverage"] == args.cov and rec.get("coverage_normal", rec["coverage"]) == cov_n \
+                                and rec.get("str_fraction", 0.0) == args.str_fraction and bool(rec.get("linked", False)) == bool(args.linked) and world == 1:
+                            if rec.get("kernel_fingerprint") != fp:
+                                out["roofline"]["traffic_note"] = (f"profiles/{name} holds PMC passes for this workload, but taken on other kernels (fingerprint "
+                                                                   f"{rec.get('kernel_fingerprint')}, these are {fp}): not quoted; re-run tools/profile_round6.sh")
+                                break
+                            out["roofline"]["traffic"] = int((rec["FETCH_SIZE_KB"] / rec.get("fetch_calibration", 1.0) + rec["WRITE_SIZE_KB"]) * 1024)
+                            out["roofline"]["traffic_fetch_write"] = [int(rec["FETCH_SIZE_KB"] * 1024), int(rec["WRITE_SIZE_KB"] * 1024)]
+                            out["roofline"]["traffic_note"] = rec["note"]
+                            out["roofline"]["traffic_kernel_fingerprint"] = fp
+                            break
+            except (OSError, KeyError, ValueError):
+                pass
+            if args.cpu_sample and world == 1:
+                out["cpu_baseline"] = cpu_baseline(batch, params, variants, args.cpu_sample, args.cpu_sample_all)
         for e2 in engs:
             e2.close()
-        if world == 1 and not args.no_bam:
+        if args.full and world == 1 and not args.no_bam:
             # BASELINE config 2's 5 Mb contig (49 981 windows; every record and the VCF of this very input against the oracle:
             # tools/e2e_parity.py, profiles/r6_e2e_parity_5mb.json)
             bam = bam_e2e(os.path.join(ROOT, "build", "scan5m"), ["--reg", "chr22:1000-4999000"], [5000000, 30, 30, 14], "5 Mb contig, 30x/30x, 2x150 bp")
@@ -640,7 +695,7 @@ def main():
                     c3["n_process_route_one_rank"] = {"windows_per_s": r1["value"], "wall_s_all_runs": r1["wall_s_all_runs"], "vcf_md5_equal": r1["vcf_md5"] == c3["vcf_md5"],
                                                       "what": "the same input through lancet_gpu --ranks 1: records packed (keys + reduction), gathered over RCCL, replayed on rank 0"}
                 out["config3_proxy"] = c3
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             out["configs"] = ([out.pop("config3_proxy")] if "config3_proxy" in out else []) + [
                 side_config(engine.Engine, params, "config 2 at 60x/60x", 8192, 60.0, 60.0, 8),
                 side_config(engine.Engine, params, "config 4: 100x tumor / 40x normal, 30 % STR + 5 % low complexity", 4096, 100.0, 40.0, 8,

@@ -6,6 +6,8 @@ tests/golden/<case>.vcf and <case>.trace.txt were written by the unmodified refe
   * the digest of the reference's `-v` trace: every k attempt and its rejection reason, node/edge/span counts
     after each graph stage, source/sink anchors, every path and every transcript with its coverages.
 CPU only."""
+import os
+
 import numpy as np
 import pytest
 
@@ -45,10 +47,13 @@ def _rand_seq(rng, n):
     return "".join("ACGT"[i] for i in rng.integers(0, 4, size=n))
 
 
-@pytest.mark.skipif(not oracle.ref_align_available(), reason="oracle/_ref/libalign_ref.so not built")
-def test_alignment_restatement_equals_reference_align_cc():
-    """oracle global_align_aff vs the reference's own align.cc compiled into oracle/_ref (real reference code)."""
+ALIGN_GOLDEN = os.path.join(gu.GOLDEN, "align_ref.tsv")
+
+
+def align_cases():
+    """The (S, T) pairs the alignment restatement is checked on: random sequences with a few edits, then degenerate shapes."""
     rng = np.random.default_rng(5)
+    pairs = []
     for it in range(60):
         n = int(rng.integers(30, 260))     # tiny S hits undefined behaviour in the reference traceback
         s = _rand_seq(rng, n)
@@ -62,11 +67,31 @@ def test_alignment_restatement_equals_reference_align_cc():
                 t[p:p] = list(_rand_seq(rng, int(rng.integers(1, 40))))
             elif t:
                 del t[p:p + int(rng.integers(1, 40))]
-        t = "".join(t) or "A"
-        assert oracle.align(s, t) == oracle.ref_align(s, t), (s, t)
-    # degenerate shapes
-    for s, t in (("A", "A"), ("A", "C"), ("ACGT", "A"), ("A", "ACGT"), ("AAAAAAAA", "AAAA"), ("ACACACAC", "ACAC")):
-        assert oracle.align(s, t) == oracle.ref_align(s, t)
+        pairs.append((s, "".join(t) or "A"))
+    return pairs + [("A", "A"), ("A", "C"), ("ACGT", "A"), ("A", "ACGT"), ("AAAAAAAA", "AAAA"), ("ACACACAC", "ACAC")]
+
+
+def load_align_golden():
+    """tests/golden/align_ref.tsv: S, T and the two aligned rows the reference's own global_align_aff returned for them
+    (tools/make_align_golden.py)."""
+    out = {}
+    with open(ALIGN_GOLDEN) as fh:
+        for line in fh:
+            s, t, a, b = line.rstrip("\n").split("\t")
+            out[(s, t)] = (a, b)
+    return out
+
+
+def test_alignment_restatement_equals_reference_align_cc():
+    """oracle global_align_aff vs the reference's own align.cc (real reference code): its answers recorded in
+    tests/golden/align_ref.tsv, and the library itself where oracle/_ref holds a build of it."""
+    golden = load_align_golden()
+    live = oracle.ref_align_available()
+    for s, t in align_cases():
+        assert (s, t) in golden, (s, t)
+        assert oracle.align(s, t) == golden[(s, t)], (s, t)
+        if live:
+            assert oracle.ref_align(s, t) == golden[(s, t)], (s, t)
 
 
 def test_std_hash_known_answers():

@@ -5,6 +5,8 @@
 #     graphs themselves -- the window kernel's traffic here is an upper bound of a normal launch's;
 #   * trim + pack runs on the device (LANCET_PREP=device): prep_kernel reads and writes a byte count known from the batch, in this
 #     code's own access widths (bytes and 4-byte words, coalesced) -- the calibration the guide asks for before trusting an absolute.
+# The bench line of each pass is kept for its roofline (algorithmic bytes, kernel times: tools/traffic_json.py): --full.
+BENCH_ARGS="--full $BENCH_ARGS"
 cd /root/repo; mkdir -p gpurun_out; cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   d=/root/repo/gpurun_out/pmc_$c; rm -rf $d

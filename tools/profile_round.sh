@@ -2,7 +2,8 @@
 # which is what the roofline figures of the bench line are measured on), PMC traffic passes, kernel resources, the re-run tier's kernel.
 TAG=${1:-r3_x}
 cd /root/repo; mkdir -p gpurun_out/$TAG
-timeout 600 python bench.py > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err; tail -1 gpurun_out/$TAG/bench.json | cut -c1-300
+O=$(echo */"$TAG")          # (the folder made on the line above)
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 rm -rf /root/repo/gpurun_out/$TAG/kt
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/gpurun_out/$TAG/kt -- python /root/repo/bench.py --cpu-sample 0 --no-configs --in-flight 1 > /root/repo/gpurun_out/$TAG/kt.log 2>&1

@@ -4,7 +4,7 @@
 # BAMs are there), the SQ counter passes of the build kernel.
 TAG=${1:-r6_final}
 cd /root/repo; O=gpurun_out/$TAG; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 rm -rf /root/repo/$O/kt
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/kt -- python /root/repo/bench.py --steps 20 --settle 0 --cpu-sample 0 --no-configs --no-bam --in-flight 1 > /root/repo/$O/kt.log 2>&1
