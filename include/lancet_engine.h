@@ -253,6 +253,20 @@ int lancet_engine_trace(lancet_engine *e, const uint32_t **evt_len, const uint32
 char *lancet_trace_format(const uint32_t *words, uint32_t n_words, int32_t idx1, const char *hdr, const char *chrom,
                           int32_t start, int32_t end, int32_t dfs_limit);
 
+/* ---- test hook: the device global_align_aff (reference src/align.cc:235-364) alone, on one pair of ACGT strings ----------
+ * S has 1..1024 bases, T 1..16383 (the traceback keeps positions of T in 14 bits; longer: LANCET_E_ARG).  The aligned rows go to
+ * S_aln / T_aln (cap bytes each, NUL-terminated).  mode:
+ *   0  band of 128 diagonals first, the full matrix when the band cannot certify itself (what a window runs)
+ *   1  the full matrix only
+ *   2  the band only; LANCET_E_STATE when it did not certify itself
+ *   4, 5, 6  modes 0, 1, 2 through the 512-lane build of the same source (the re-run tier's kernel)
+ * LANCET_E_UNSUPPORTED: the reference's own traceback leaves its matrix on this pair (undefined behaviour there; a window
+ * with such a path is reported LANCET_W_OVERFLOW), or the rows do not fit cap.  lancet_debug_align is mode 0.
+ * lancet_engine_create refuses max_indel_len above 15103 (LANCET_E_ARG) for the same 14 bits: path strings have up to
+ * 1024 + max_indel_len + 256 bases. */
+int lancet_debug_align(lancet_engine *e, const char *S, const char *T, char *S_aln, char *T_aln, int cap);
+int lancet_debug_align_mode(lancet_engine *e, const char *S, const char *T, char *S_aln, char *T_aln, int cap, int mode);
+
 /* ---- host side of the seam: Variant_t normalisation + VariantDB + VCF ----------
  * reference src/Variant.hh:106-172 (ctor), src/VariantDB.cc:28-91 (addVar), :93-179 (VCF),
  * src/Variant.cc:39-223 (printVCF). */

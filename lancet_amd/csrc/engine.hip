@@ -204,20 +204,11 @@ __global__ void __launch_bounds__(256) prep_kernel(const lancet_params *P, int n
     good[g0 + wv] = v;
   }
 }
-// test hook: global_align_aff alone (align_fill + align_traceback) on one pair of strings
+// test hook: global_align_aff alone on one pair of strings (kernels.h align_test_body)
 __global__ void __launch_bounds__(LANCET_WG * 2) align_test_kernel(const EngineCaps *C, Work *work, const uint8_t *Sx, int n, const uint8_t *Tx, int m, int *out_len, int mode) {
-  LC_WS &S = *(LC_WS *)&lc_shared;
-  Ctx c; c.P = nullptr; c.B = nullptr; c.C = (LC_GLOBAL const EngineCaps *)C; c.W = (LC_GLOBAL Work *)work; c.OUT = nullptr; c.S = &S;
-  LC_CTX_PUBLISH(c);
-  WG_LANE0 { S.overflow = 0; }
-  WG_SYNC();
-  if (mode == 1 || !align_fill_band(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m)) {     // mode 1: the full matrix only
-    if (mode == 2) { WG_LANE0 { *out_len = -2; } return; }                                                          // mode 2: the band only (-2: not certified)
-    align_fill(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m);
-  }
-  { const int L = align_traceback_wg(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m); WG_LANE0 { S.tmp0 = L; *out_len = S.overflow ? -1 : L; } }
-  align_traceback_fill(c, (LC_GLOBAL const uint8_t *)Sx, (LC_GLOBAL const uint8_t *)Tx, wg_bcast(&S.tmp0));
+  align_test_body(C, work, Sx, n, Tx, m, out_len, mode);
 }
+int lc_launch_align_test_fat(hipStream_t stream, const EngineCaps *C, Work *work, const uint8_t *Sx, int n, const uint8_t *Tx, int m, int *out_len, int mode);   // window_fat.hip
 
 __global__ void ref_code_kernel(const char *ref, uint8_t *codes, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -264,6 +255,7 @@ struct lancet_engine {
   EngineCaps caps;      // tier 1
   EngineCaps caps2;     // tier 2 (re-run of overflowed windows)
   DevBuf d_caps2, d_works2, d_workmem2, d_out2, d_winlist, d_skip;
+  DevBuf dbg_mem, dbg_caps, dbg_work, dbg_s, dbg_t, dbg_len;      // lancet_debug_align_mode: kept from call to call
   int n_slots2 = 0;
   uint32_t node_cap1 = 16384;   // tier-1 node limit per window when LANCET_NODE_CAP1 sets it (else from the batch, lc_upload)
   bool node_cap1_env = false;
@@ -375,6 +367,11 @@ int lancet_engine_create(const lancet_params *p, int device, lancet_engine **out
   if (!p || !out) return LANCET_E_ARG;
   *out = nullptr;
   if (p->max_k > 127 || p->min_k < 3 || p->max_unit_len > 8) return LANCET_E_UNSUPPORTED;
+  // path_cap (host_common.h lc_caps: max_w + max_indel_len + 256, max_w up to LC_MAXW) must fit the path index of the traceback notes
+  if (p->max_indel_len < 0 || (long long)LC_MAXW + (long long)p->max_indel_len + 256 > (long long)LC_NOTE_JMAX) {
+    fprintf(stderr, "lancet_engine_create: max_indel_len %d is outside 0..%d (the alignment keeps path positions in 14 bits)\n", (int)p->max_indel_len, LC_NOTE_JMAX - LC_MAXW - 256);
+    return LANCET_E_ARG;
+  }
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return LANCET_E_NO_DEVICE;
   lancet_engine *e = new lancet_engine();
@@ -451,7 +448,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   DevBuf *all[] = {&e->d_params, &e->d_batch, &e->d_caps, &e->d_out, &e->d_works, &e->d_chr, &e->d_refstart, &e->d_refoff, &e->d_refasc,
                    &e->d_refcodes, &e->d_readbegin, &e->d_seqoff, &e->d_seq, &e->d_qual, &e->d_label, &e->d_strand, &e->d_mate, &e->d_mapped,
                    &e->d_rinfo, &e->d_name, &e->d_bw, &e->d_gw, &e->d_bases, &e->d_good, &e->d_variants, &e->d_blob, &e->d_counters,
-                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage};
+                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage};
   for (DevBuf *b : all) b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->evb0) (void)hipEventDestroy(e->evb0);
@@ -1190,39 +1187,51 @@ int lancet_engine_trace(lancet_engine *e, const uint32_t **evt_len, const uint32
   return LANCET_OK;
 }
 
-// test hook: runs the device alignment on (S, T) (ACGT strings, |S| <= LC_MAXW); writes the aligned strings.
+// test hook: runs the device alignment on (S, T) (ACGT strings, |S| <= LC_MAXW, |T| <= LC_NOTE_JMAX); writes the aligned strings.
 // mode 0: band first, full matrix when the band is not certified (what the window kernel does); 1: full matrix only; 2: band only
-// (LANCET_E_STATE when the band could not be certified)
+// (LANCET_E_STATE when the band could not be certified); + 4: the same through the LC_FAT_LANES-lane build of the source (window_fat.hip).
+// LANCET_E_UNSUPPORTED: the reference's traceback leaves its matrix on this pair (undefined there; a window reports an overflow).
 int lancet_debug_align_mode(lancet_engine *e, const char *S, const char *T, char *S_aln, char *T_aln, int cap, int mode);
 int lancet_debug_align(lancet_engine *e, const char *S, const char *T, char *S_aln, char *T_aln, int cap) { return lancet_debug_align_mode(e, S, T, S_aln, T_aln, cap, 0); }
 int lancet_debug_align_mode(lancet_engine *e, const char *S, const char *T, char *S_aln, char *T_aln, int cap, int mode) {
-  if (!e || !S || !T) return LANCET_E_ARG;
+  if (!e || !S || !T || !S_aln || !T_aln) return LANCET_E_ARG;
+  if (mode < 0 || mode > 6 || (mode & 3) == 3) { e->err = "debug_align: mode is 0, 1 or 2, + 4 for the fat form"; return LANCET_E_ARG; }
+  const size_t ns = strlen(S), ms = strlen(T);
+  if (ns < 1 || ms < 1 || ns > (size_t)LC_MAXW) { e->err = "debug_align: S has 1.." + std::to_string(LC_MAXW) + " bases, T at least one"; return LANCET_E_ARG; }
+  if (ms > (size_t)LC_NOTE_JMAX) { e->err = "debug_align: T is longer than " + std::to_string(LC_NOTE_JMAX) + " bases (the traceback notes keep its positions in 14 bits)"; return LANCET_E_ARG; }
   HIPCHK(e, hipSetDevice(e->device));
-  int n = (int)strlen(S), m = (int)strlen(T);
-  if (n < 1 || m < 1 || n > LC_MAXW) return LANCET_E_ARG;
+  const int n = (int)ns, m = (int)ms;
   EngineCaps caps; memset(&caps, 0, sizeof(caps));
-  caps.reads_cap = 4; caps.occ_cap = 64; caps.node_cap = 16; caps.table_cap = 32; caps.bucket_cap = 32; caps.special_cap = 4; caps.surv_cap = 4;
+  caps.reads_cap = 4; caps.node_cap = 16; caps.table_cap = 32; caps.bucket_cap = 32; caps.special_cap = 4; caps.surv_cap = 4;
+  caps.occ_cap = (uint32_t)(n + m) + 72;                     // (Work::scratch, where the traceback keeps a note per column, has occ_cap words)
   caps.seq_cap = 64; caps.queue_cap = 4; caps.path_cap = (uint32_t)m + 8; caps.max_k = 16; caps.qv_cap = 64;
   caps.max_w = std::max<uint32_t>(LC_MAXW_DEFAULT, ((uint32_t)n + 63u) & ~63u);
   size_t bytes = lc_work_carve(nullptr, nullptr, caps);
-  DevBuf mem, dcaps, dwork, ds, dt, dl;
+  DevBuf &mem = e->dbg_mem, &dcaps = e->dbg_caps, &dwork = e->dbg_work, &ds = e->dbg_s, &dt = e->dbg_t, &dl = e->dbg_len;
   std::vector<uint8_t> sc(n), tc(m);
   auto code = [](char b) -> uint8_t { switch (b) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; } return 4; };
   for (int i = 0; i < n; ++i) sc[i] = code(S[i]);
   for (int i = 0; i < m; ++i) tc[i] = code(T[i]);
   if (mem.ensure(bytes) || dcaps.ensure(sizeof(caps)) || dwork.ensure(sizeof(Work)) || ds.ensure(n) || dt.ensure(m) || dl.ensure(4)) return LANCET_E_OOM;
   Work w; lc_work_carve(&w, (char *)mem.p, caps);
+  int L = -3;
   HIPCHK(e, lc_copy(e, dcaps.p, &caps, sizeof(caps), hipMemcpyHostToDevice));
   HIPCHK(e, lc_copy(e, dwork.p, &w, sizeof(w), hipMemcpyHostToDevice));
   HIPCHK(e, lc_copy(e, ds.p, sc.data(), n, hipMemcpyHostToDevice));
   HIPCHK(e, lc_copy(e, dt.p, tc.data(), m, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(align_test_kernel, dim3(1), dim3(LANCET_WG), 0, e->stream, (const EngineCaps *)dcaps.p, (Work *)dwork.p, (const uint8_t *)ds.p, n,
-                     (const uint8_t *)dt.p, m, (int *)dl.p, mode);
+  HIPCHK(e, lc_copy(e, dl.p, &L, 4, hipMemcpyHostToDevice));
+  if (mode & 4) {
+    const int lrc = lc_launch_align_test_fat(e->stream, (const EngineCaps *)dcaps.p, (Work *)dwork.p, (const uint8_t *)ds.p, n, (const uint8_t *)dt.p, m, (int *)dl.p, mode & 3);
+    if (lrc != 0) { e->err = "debug_align: launch of the fat form failed"; return LANCET_E_HIP; }
+  } else {
+    hipLaunchKernelGGL(align_test_kernel, dim3(1), dim3(LANCET_WG), 0, e->stream, (const EngineCaps *)dcaps.p, (Work *)dwork.p, (const uint8_t *)ds.p, n,
+                       (const uint8_t *)dt.p, m, (int *)dl.p, mode & 3);
+  }
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  int L = 0;
   HIPCHK(e, lc_copy(e, &L, dl.p, 4, hipMemcpyDeviceToHost));
   int rc = LANCET_OK;
   if (L == -2) rc = LANCET_E_STATE;
+  else if (L == -3) { e->err = "debug_align: the kernel wrote no result"; rc = LANCET_E_HIP; }
   else if (L < 0 || L + 1 > cap) rc = LANCET_E_UNSUPPORTED;
   else {
     const int acap = (int)caps.max_w + (int)caps.path_cap + 2;
@@ -1230,7 +1239,6 @@ int lancet_debug_align_mode(lancet_engine *e, const char *S, const char *T, char
     HIPCHK(e, lc_copy(e, T_aln, w.aln + acap, L, hipMemcpyDeviceToHost));
     S_aln[L] = 0; T_aln[L] = 0;
   }
-  mem.release(); dcaps.release(); dwork.release(); ds.release(); dt.release(); dl.release();
   return rc;
 }
 

@@ -4548,6 +4548,9 @@ DEVNI int align_traceback_wg(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOB
   return wg_bcast(&S.al_L);
 #endif
 }
+// A note keeps j in 14 bits (and i in 16): the longest path string the notes can hold.  lancet_engine_create refuses parameters whose
+// path_cap is above it, the test hooks refuse such a string.
+#define LC_NOTE_JMAX 0x3FFF
 // all lanes: the aligned strings from the noted columns (noted from the end of the alignment backwards)
 DEVNI void align_traceback_fill(Ctx &c, LC_GLOBAL const uint8_t *Sx, LC_GLOBAL const uint8_t *Tx, int L) {
   LC_GLOBAL Work &W = *LC_CTX(c).W;
@@ -4562,6 +4565,25 @@ DEVNI void align_traceback_fill(Ctx &c, LC_GLOBAL const uint8_t *Sx, LC_GLOBAL c
   }
   WG_SYNC();
 }
+
+#ifndef LANCET_WAVE_EMU
+// test hook: global_align_aff alone (band / full fill, wave-wide traceback, aligned strings) on one pair of strings; the body of
+// align_test_kernel (engine.hip, one wave) and align_test_kernel_fat (window_fat.hip, LC_FAT_LANES lanes).
+// mode 0: band first, full matrix when the band is not certified; 1: full matrix only; 2: band only (*out_len = -2: not certified).
+DEV void align_test_body(const EngineCaps *C, Work *work, const uint8_t *Sx, int n, const uint8_t *Tx, int m, int *out_len, int mode) {
+  LC_WS &S = *(LC_WS *)&lc_shared;
+  Ctx c; c.P = nullptr; c.B = nullptr; c.C = (LC_GLOBAL const EngineCaps *)C; c.W = (LC_GLOBAL Work *)work; c.OUT = nullptr; c.S = &S;
+  LC_CTX_PUBLISH(c);
+  WG_LANE0 { S.overflow = 0; }
+  WG_SYNC();
+  if (mode == 1 || !align_fill_band(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m)) {
+    if (mode == 2) { WG_LANE0 { *out_len = -2; } return; }
+    align_fill(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m);
+  }
+  { const int L = align_traceback_wg(c, (LC_GLOBAL const uint8_t *)Sx, n, (LC_GLOBAL const uint8_t *)Tx, m); WG_LANE0 { S.tmp0 = L; *out_len = S.overflow ? -1 : L; } }
+  align_traceback_fill(c, (LC_GLOBAL const uint8_t *)Sx, (LC_GLOBAL const uint8_t *)Tx, wg_bcast(&S.tmp0));
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------------
 // processPath (reference src/Graph.cc:788-1220) + Transcript_t::computeStats (reference src/Transcript.hh:123-226)

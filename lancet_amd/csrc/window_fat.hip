@@ -14,3 +14,13 @@ int lc_launch_window_fat(int slots, hipStream_t stream, const lancet_params *P, 
   hipLaunchKernelGGL(window_kernel_fat, dim3(slots), dim3(LC_FAT_LANES), 0, stream, P, B, C, works, OUT);
   return (int)hipGetLastError();
 }
+
+// test hook: global_align_aff alone through this build of the source (kernels.h align_test_body; lancet_debug_align_mode, mode + 4)
+__global__ void __launch_bounds__(LC_FAT_LANES) align_test_kernel_fat(const EngineCaps *C, Work *work, const uint8_t *Sx, int n, const uint8_t *Tx, int m, int *out_len, int mode) {
+  align_test_body(C, work, Sx, n, Tx, m, out_len, mode);
+}
+
+int lc_launch_align_test_fat(hipStream_t stream, const EngineCaps *C, Work *work, const uint8_t *Sx, int n, const uint8_t *Tx, int m, int *out_len, int mode) {
+  hipLaunchKernelGGL(align_test_kernel_fat, dim3(1), dim3(LC_FAT_LANES), 0, stream, C, work, Sx, n, Tx, m, out_len, mode);
+  return (int)hipGetLastError();
+}

@@ -257,13 +257,14 @@ class Engine:
         self._chk(self.L.lancet_engine_phase_times(self.h, C.byref(p)))
         return np.ctypeslib.as_array(p, shape=(self._batch.n_windows, 16)).astype(np.float64) * 1e-8
 
-    def debug_align(self, s: str, t: str, mode: int = 0):
+    def debug_align(self, s: str, t: str, mode: int = 0, fat: bool = False):
         """Test hook: the device global_align_aff on one pair of strings.  mode 0: banded matrix with the full one as fall-back (what
-        the window kernel runs), 1: full matrix only, 2: band only -- returns None when the band could not be certified."""
+        the window kernel runs), 1: full matrix only, 2: band only -- returns None when the band could not be certified.  fat: through
+        the 512-lane build of the kernels (the re-run tier's).  EngineError where the reference's traceback is undefined on the pair."""
         cap = len(s) + len(t) + 8
         a = C.create_string_buffer(cap)
         b = C.create_string_buffer(cap)
-        rc = self.L.lancet_debug_align_mode(self.h, s.encode(), t.encode(), a, b, cap, mode)
+        rc = self.L.lancet_debug_align_mode(self.h, s.encode(), t.encode(), a, b, cap, mode + (4 if fat else 0))
         if rc == -6 and mode == 2:
             return None
         self._chk(rc)

@@ -503,7 +503,9 @@ struct Path {
 
 // ---- global_align_aff, reference src/align.cc:235-364 (scores :28-31, tie rules :85-105) ------------------
 struct Cell { int score = 0; char tb = '*'; };
-void global_align_aff(const std::string &S, const std::string &T, std::string &S_aln, std::string &T_aln) {
+// Returns false where the reference's traceback would leave the matrix (S[-1] under forcex at i = 0, T[-1] under forcey at j = 0:
+// undefined behaviour there; the kernels report such a pair as a work-space overflow, kernels.h align_traceback).
+bool global_align_aff(const std::string &S, const std::string &T, std::string &S_aln, std::string &T_aln) {
   const int MATCH = 2, MISMATCH = -4, GAP_OPEN = -8, GAP_EXTEND = -1;
   S_aln.clear(); T_aln.clear();
   int n = S.length(), m = T.length();
@@ -528,15 +530,16 @@ void global_align_aff(const std::string &S, const std::string &T, std::string &S
   while (i > 0 || j > 0) {
     char t = M[i][j].tb;
     if (t == '*') break;
-    else if (forcex) { ts.push_back(S[i - 1]); tt.push_back('-'); if (X[i][j].tb == '<') forcex = false; --i; }
+    else if (forcex) { if (i < 1) return false; ts.push_back(S[i - 1]); tt.push_back('-'); if (X[i][j].tb == '<') forcex = false; --i; }
     else if (t == '<') { ts.push_back(S[i - 1]); tt.push_back('-'); if (X[i][j].tb == '-') forcex = true; --i; }
-    else if (forcey) { ts.push_back('-'); tt.push_back(T[j - 1]); if (Y[i][j].tb == '^') forcey = false; --j; }
+    else if (forcey) { if (j < 1) return false; ts.push_back('-'); tt.push_back(T[j - 1]); if (Y[i][j].tb == '^') forcey = false; --j; }
     else if (t == '^') { ts.push_back('-'); tt.push_back(T[j - 1]); if (Y[i][j].tb == '|') forcey = true; --j; }
     else if (t == '\\') { ts.push_back(S[i - 1]); tt.push_back(T[j - 1]); --i; --j; }
     else break;
   }
   S_aln.assign(ts.rbegin(), ts.rend());
   T_aln.assign(tt.rbegin(), tt.rend());
+  return true;
 }
 
 struct OutVariant {
@@ -561,6 +564,7 @@ struct Graph {
   std::vector<ReadInfo> reads;
   std::vector<OutVariant> *out = nullptr;
   int cur_window = 0, cur_chr = 0, emit_seq = 0;
+  bool align_undefined = false;                                                      // processPath met a pair the reference's traceback walks out of (global_align_aff)
   uint64_t n_kmers = 0; uint32_t max_nodes = 0, sum_nodes = 0; int n_builds = 0;
   std::unordered_map<std::string, std::set<uint32_t>> bxT, bxN;                       // Graph_t::bx_table_tmr / _nml
 
@@ -1059,7 +1063,9 @@ struct Graph {
     std::vector<Cov> covN = path->covDistr('N'), covT = path->covDistr('T');
     std::string pathseq = path->str();
     int hd = HammingDistance(refseq, pathseq);
-    if (hd == -1 || hd > HD_CUTOFF) global_align_aff(refseq, pathseq, ref_aln, path_aln);
+    if (hd == -1 || hd > HD_CUTOFF) {
+      if (!global_align_aff(refseq, pathseq, ref_aln, path_aln)) { align_undefined = true; return; }   // the engine reports the window LANCET_W_OVERFLOW
+    }
     else { ref_aln = refseq; path_aln = pathseq; }
     if (verbose) {      // printVerticalAlignment side effects (Graph.cc:749-783): the bp counters
       for (size_t i = 0; i < ref_aln.length(); ++i) {
@@ -1267,7 +1273,7 @@ int processGraph(Graph &g, RefInfo *refinfo, int graphCnt, lancet_window_stats *
     if (cycleInGraph) tr << " Found cycle in assembly" << std::endl;
     tr << "FINISHED" << std::endl;
   }
-  st->status = processed ? LANCET_W_OK : LANCET_W_K_EXHAUSTED;
+  st->status = g.align_undefined ? LANCET_W_OVERFLOW : (processed ? LANCET_W_OK : LANCET_W_K_EXHAUSTED);
   return 1;
 }
 
@@ -1307,7 +1313,7 @@ void *lancet_oracle_run(const lancet_params *P, const lancet_window_batch *b, co
     ref.refstart = b->ref_start[w];
     ref.refend = ref.refstart + (int)ref.rawseq.length();
     ref.hdr = hdrs ? hdrs[w] : (ref.chr + ":" + std::to_string(ref.refstart) + "-" + std::to_string(ref.refend));
-    g.cur_window = w; g.cur_chr = b->chr_id[w]; g.emit_seq = 0;
+    g.cur_window = w; g.cur_chr = b->chr_id[w]; g.emit_seq = 0; g.align_undefined = false;
     g.n_kmers = 0; g.max_nodes = 0; g.sum_nodes = 0; g.n_builds = 0;
     for (uint32_t r = b->read_begin[w]; r < b->read_begin[w + 1]; ++r) {             // Graph_t::addAlignment, Graph.cc:487-501
       ReadInfo ri;
@@ -1357,8 +1363,8 @@ void lancet_oracle_free(void *h) { delete (OracleResult *)h; }
 // Stand-alone pieces, exported so tests can pin kernels individually.
 int lancet_oracle_align(const char *S, const char *T, char *S_aln, char *T_aln, int cap) {
   std::string a, b;
-  global_align_aff(S, T, a, b);
-  if ((int)a.size() + 1 > cap) return -1;
+  if (!global_align_aff(S, T, a, b)) return -1;                // undefined in the reference (see global_align_aff)
+  if ((int)a.size() + 1 > cap) return -2;
   memcpy(S_aln, a.c_str(), a.size() + 1); memcpy(T_aln, b.c_str(), b.size() + 1);
   return (int)a.size();
 }

@@ -84,11 +84,15 @@ def run(batch, params=None, verbose: bool = False):
 
 
 def align(S: str, T: str):
+    """The two aligned rows, or None where the reference's traceback would leave its matrix (undefined there; the engine reports an
+    overflow for such a pair)."""
     L = lib()
     cap = len(S) + len(T) + 8
     a = C.create_string_buffer(cap)
     b = C.create_string_buffer(cap)
     n = L.lancet_oracle_align(S.encode(), T.encode(), a, b, cap)
+    if n == -1:
+        return None
     assert n >= 0
     return a.value.decode(), b.value.decode()
 

@@ -186,12 +186,13 @@ extern "C" int lancet_emu_find_tandems(const uint8_t *codes, int n, int pos, int
   return a ? 1 : 0;
 }
 
-// global_align_aff through the emulated kernels: mode 0 band with fall-back, 1 full matrix, 2 band only (returns -2 when not certified)
+// global_align_aff through the emulated kernels: mode 0 band with fall-back, 1 full matrix, 2 band only (returns -2 when not certified);
+// -1: the reference's traceback leaves its matrix (undefined there); -3: a string too long for the hook
 extern "C" int lancet_emu_align(const char *Sa, const char *Ta, char *S_aln, char *T_aln, int cap, int mode) {
   int n = (int)strlen(Sa), m = (int)strlen(Ta);
-  if (n < 1 || m < 1 || n > LC_MAXW) return -1;
+  if (n < 1 || m < 1 || n > LC_MAXW || m > LC_NOTE_JMAX) return -3;          // refused, as lancet_debug_align_mode refuses it
   EngineCaps caps; memset(&caps, 0, sizeof(caps));
-  caps.reads_cap = 4; caps.occ_cap = 64; caps.node_cap = 16; caps.table_cap = 32; caps.bucket_cap = 32; caps.special_cap = 4; caps.surv_cap = 4;
+  caps.reads_cap = 4; caps.occ_cap = (uint32_t)(n + m) + 72; caps.node_cap = 16;     // (occ_cap words of Work::scratch: a traceback note per column) caps.table_cap = 32; caps.bucket_cap = 32; caps.special_cap = 4; caps.surv_cap = 4;
   caps.seq_cap = 64; caps.queue_cap = 4; caps.path_cap = (uint32_t)m + 8; caps.max_k = 16; caps.qv_cap = 64;
   caps.max_w = LC_MAXW_DEFAULT > (((uint32_t)n + 63u) & ~63u) ? LC_MAXW_DEFAULT : (((uint32_t)n + 63u) & ~63u);
   size_t bytes = lc_work_carve(nullptr, nullptr, caps);

@@ -6,6 +6,7 @@ import sys
 
 import pytest
 
+import align_cases as ac
 import golden_util as gu
 from lancet_amd import abi
 from oracle import oracle
@@ -695,3 +696,80 @@ def test_fat_source_on_a_window_of_more_than_65535_reads(linked, fat_emu):
 @pytest.mark.parametrize("seed", [0, 1])
 def test_fat_source_on_random_linked_read_windows(seed, fat_emu):
     test_emulated_kernels_match_oracle_on_random_linked_read_windows(seed)
+
+
+def _emu_build(fat):
+    """The emulator build without (libemu.so) or with LANCET_FAT (libemu_fat.so)."""
+    was = emu.FAT[0]
+    emu.FAT[0] = fat
+    try:
+        return emu.lib()
+    finally:
+        emu.FAT[0] = was
+
+
+# what the band of the emulated kernels has to certify per family (the whole of `len` and `str`; in `gap` the indels of up to 111 bases)
+EMU_CERTIFIED_MIN = {"len": 62, "str": 108, "gap": 320, "edge": 20, "tiny": 6, "unrel": 0, "lowc": 0}
+
+
+@pytest.mark.parametrize("fat", [False, True], ids=["thin", "fat"])
+@pytest.mark.parametrize("fam", ac.FAMILIES)
+def test_emulated_alignment_equals_reference_on_tie_rich_and_boundary_pairs(fam, fat):
+    """Both emulator builds on the table of tests/align_cases.py against the reference's own answers (tests/golden/align_edge_ref.tsv):
+    the full matrix and the band with fall-back must equal them, the band alone must refuse or equal them, and a pair on which the
+    reference's traceback leaves its matrix must be reported undefined (an overflow in a window), never answered."""
+    L = _emu_build(fat)
+    golden = ac.golden()
+    certified = 0
+    for cid, s, t in ac.by_family(fam):
+        want = golden[cid]
+        full, both, band = (ac.emu_align(L, s, t, mode) for mode in (1, 0, 2))
+        assert full == want, cid
+        assert both == want, cid
+        assert band is None or band == want, cid
+        certified += band is not None and band != ac.UNDEFINED
+        if want == ac.UNDEFINED:
+            assert oracle.align(s, t) is None, cid
+    print(f"emulator ({'fat' if fat else 'thin'}) band certified {certified} of {len(ac.by_family(fam))} in {fam}")
+    assert certified >= EMU_CERTIFIED_MIN[fam], (fam, certified)
+    assert certified >= ac.CERTIFY_FLOOR.get(fam, 0)
+
+
+def test_band_refuses_a_path_just_outside_it_and_holds_one_on_its_edge_lane():
+    """The `edge` pairs: two opposite indels take the best path x diagonals off the main diagonal and back to the corner's.  The band
+    holds 128 offsets around the two corner diagonals, w below the lower one and w + 1 (|m - n| even) above the upper one, and its
+    certificate compares the score with the best alignment that leaves through the NEARER edge (gaps of w + 1).  So a path down to the
+    lowest offset (lane 0) certifies, a path up to offset w above (lane 63's first offset) certifies, one on the topmost offset (w + 1
+    above, lane 63's second) is computed inside the band but scores 2 below the bound and must be refused like the ones outside."""
+    L = _emu_build(False)
+    seen = set()
+    for cid, s, t in ac.by_family("edge"):
+        d, direction, x = cid.split("/")[1].split("_")[:3]
+        d, x = int(d[1:]), int(x[1:])
+        w = (127 - d) // 2
+        last = (-w + 127) if direction == "up" else d + w           # the outermost offset of the band on that side, from the main diagonal
+        last_certified = last - 1 if direction == "up" else last
+        band = ac.emu_align(L, s, t, 2)
+        assert (band is not None) == (x <= last_certified), (cid, last)
+        seen.add((d, direction, x - last))
+    assert {k[2] for k in seen} == {-2, -1, 0, 1, 2} and len(seen) == 20
+
+
+@pytest.mark.parametrize("fat", [False, True], ids=["thin", "fat"])
+def test_emulated_alignment_of_a_path_at_the_limit_of_the_traceback_notes(fat):
+    """The traceback notes keep the position in T in 14 bits (kernels.h LC_NOTE_JMAX): T of 16 383 bases must still equal the oracle,
+    16 384 or 16 400 bases must be refused, not answered with positions that wrapped."""
+    import numpy as np
+    L = _emu_build(fat)
+    rng = np.random.default_rng(16383)
+    rs = lambda n: "".join("ACGT"[i] for i in rng.integers(0, 4, size=n))
+    s = rs(100)
+    for m in (16383, 16384, 16400):
+        for t in (s[:50] + rs(m - 100) + s[50:], rs(m - 100) + s, s + rs(m - 100)):
+            for mode in (0, 1):
+                got = ac.emu_align(L, s, t, mode)
+                if m > 16383:
+                    assert got == ac.REFUSED, (m, mode)
+                else:
+                    want = oracle.align(s, t)
+                    assert got == (ac.UNDEFINED if want is None else want), (m, mode)

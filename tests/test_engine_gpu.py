@@ -2,13 +2,19 @@
 (b) the committed reference goldens (VCF + `-v` stage trace).  Bit-exact: everything is integer/index work
 except four float coverages per node, which must round exactly like the reference (no tolerance)."""
 import os
+import sys
+import time
 
 import numpy as np
 import pytest
 
+import align_cases as ac
 import golden_util as gu
 from lancet_amd import abi, engine
 from oracle import oracle
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+import emu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -191,6 +197,110 @@ def test_device_alignment_equals_reference_align_cc():
         n_band += band is not None
     assert n_band >= 20
     eng.close()
+
+
+@pytest.fixture(scope="module")
+def align_engine():
+    """One engine for the whole alignment table (the hook keeps its device buffers from call to call), made with the parameters of the
+    small batch it has to assemble afterwards."""
+    meta, batch, kept, (min_k, max_k) = gu.case_batch("cfg1_k25")
+    eng = engine.Engine(abi.default_params(min_k=min_k, max_k=max_k), device=0)
+    yield eng
+    eng.close()
+
+
+def _small_batch_is_assembled(eng):
+    meta, batch, kept, (min_k, max_k) = gu.case_batch("cfg1_k25")
+    variants, stats = eng.process(batch)
+    ov, ostats, _ = oracle.run(batch, eng.params)
+    assert variants == ov and len(variants) == 1
+    assert [s["status"] for s in stats] == [s["status"] for s in ostats] and stats[0]["n_kmers"] == ostats[0]["n_kmers"]
+
+
+def _emu_thin():
+    was = emu.FAT[0]
+    emu.FAT[0] = False
+    try:
+        return emu.lib()
+    finally:
+        emu.FAT[0] = was
+
+
+@pytest.mark.parametrize("fat", [False, True], ids=["wave", "fat"])
+@pytest.mark.parametrize("fam", ac.FAMILIES)
+def test_device_alignment_on_tie_rich_and_boundary_pairs(align_engine, fam, fat):
+    """The device forms of global_align_aff -- the systolic full-matrix fill, the two-offsets-per-lane band fill and the wave-wide
+    traceback, none of which the emulator runs -- on the table of tests/align_cases.py, through the one-wave hook and through the
+    512-lane build of the same source (fat), against what the reference's own align.cc answered (tests/golden/align_edge_ref.tsv).
+      * modes 0 (band, full matrix as fall-back) and 1 (full matrix) equal the fixture; mode 2 (band alone) refuses or equals it;
+      * whether the band certifies itself is the emulator's decision for the same pair: the arithmetic is the same, and a band that
+        lost a cell at a lane edge or a seam would otherwise hide behind the full-matrix fall-back;
+      * the certified pairs reach 90 % of what the emulator's band certified when the table was drawn (align_cases.CERTIFY_FLOOR);
+      * a pair on which the reference's traceback leaves its matrix is refused (LANCET_E_UNSUPPORTED: the kernel's own bounds check,
+        what a window reports as an overflow) in modes 0 and 1;
+      * the engine assembles an ordinary small batch afterwards."""
+    eng = align_engine
+    golden = ac.golden()
+    L = _emu_thin()
+    certified = 0
+    differ = []
+    t0 = time.perf_counter()
+    for cid, s, t in ac.by_family(fam):
+        want = golden[cid]
+        emu_band = ac.emu_align(L, s, t, 2)
+        if want == ac.UNDEFINED:
+            for mode in (0, 1):
+                with pytest.raises(engine.EngineError, match="unsupported"):
+                    eng.debug_align(s, t, mode=mode, fat=fat)
+            assert emu_band is None or emu_band == ac.UNDEFINED, cid
+            continue
+        assert eng.debug_align(s, t, mode=0, fat=fat) == want, cid
+        assert eng.debug_align(s, t, mode=1, fat=fat) == want, cid
+        band = eng.debug_align(s, t, mode=2, fat=fat)
+        assert band is None or band == want, cid
+        if (band is None) != (emu_band is None):
+            differ.append((cid, band is not None, emu_band is not None))
+        certified += band is not None
+    dt = time.perf_counter() - t0
+    print(f"device band ({'fat' if fat else 'wave'}) certified {certified} of {len(ac.by_family(fam))} in {fam}; {dt:.2f} s")
+    assert not differ, differ
+    assert certified >= ac.CERTIFY_FLOOR.get(fam, 0), (fam, certified)
+    _small_batch_is_assembled(eng)
+
+
+@pytest.mark.parametrize("fat", [False, True], ids=["wave", "fat"])
+def test_device_alignment_of_a_path_at_the_limit_of_the_traceback_notes(align_engine, fat):
+    """The traceback notes keep the position in T in 14 bits: T of 16 383 bases (n about 100) must still equal the oracle -- the full
+    matrix there also has its lowest scores, M(0, j) = -8 - j, in the 16-bit halves of the systolic fill's registers -- and 16 384 or
+    16 400 bases must be refused loudly (LANCET_E_ARG), not answered with positions that wrapped."""
+    eng = align_engine
+    rng = np.random.default_rng(16383)
+    s = _rand_seq(rng, 100)
+    for m in (16383, 16384, 16400):
+        for t in (s[:50] + _rand_seq(rng, m - 100) + s[50:], _rand_seq(rng, m - 100) + s, s + _rand_seq(rng, m - 100)):
+            assert len(t) == m
+            for mode in (0, 1):
+                if m > 16383:
+                    with pytest.raises(engine.EngineError, match="bad argument.*14 bits"):
+                        eng.debug_align(s, t, mode=mode, fat=fat)
+                    continue
+                want = oracle.align(s, t)
+                if want is None:
+                    with pytest.raises(engine.EngineError, match="unsupported"):
+                        eng.debug_align(s, t, mode=mode, fat=fat)
+                else:
+                    assert eng.debug_align(s, t, mode=mode, fat=fat) == want, (m, mode)
+    _small_batch_is_assembled(eng)
+
+
+def test_engine_refuses_an_indel_limit_the_traceback_notes_cannot_hold():
+    """path_cap is max_w + max_indel_len + 256 with max_w up to 1024: above 16 383 the 14-bit path index of the notes would wrap."""
+    p = abi.default_params()
+    p.max_indel_len = 15103
+    engine.Engine(p, device=0).close()
+    p.max_indel_len = 15104
+    with pytest.raises(engine.EngineError, match="bad argument"):
+        engine.Engine(p, device=0)
 
 
 def test_overflowed_windows_are_rerun_with_worst_case_workspace(monkeypatch):

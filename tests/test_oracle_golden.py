@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import align_cases as ac
 import golden_util as gu
 from lancet_amd import abi
 from oracle import oracle, vcf_oracle
@@ -92,6 +93,48 @@ def test_alignment_restatement_equals_reference_align_cc():
         assert oracle.align(s, t) == golden[(s, t)], (s, t)
         if live:
             assert oracle.ref_align(s, t) == golden[(s, t)], (s, t)
+
+
+@pytest.mark.parametrize("fam", ac.FAMILIES)
+def test_alignment_restatement_equals_reference_on_tie_rich_and_boundary_pairs(fam):
+    """The oracle's global_align_aff on the table of tests/align_cases.py (length seams, STR expansions, long gaps, paths along the edge of
+    the band, tiny and unrelated strings) against what the reference's own align.cc answered (tests/golden/align_edge_ref.tsv), and against
+    the library itself where oracle/_ref holds a build of it.  Where the reference's traceback leaves its matrix (undefined behaviour
+    there, `undefined` in the fixture) the oracle returns None -- it used to crash the process -- and the library is not called."""
+    golden = ac.golden()
+    live = oracle.ref_align_available()
+    n = 0
+    for cid, s, t in ac.by_family(fam):
+        want = golden[cid]
+        got = oracle.align(s, t)
+        if want == ac.UNDEFINED:
+            assert got is None, cid
+            continue
+        assert got == want, cid
+        if live:
+            assert oracle.ref_align(s, t) == want, cid
+        n += 1
+    assert n >= {"len": 62, "str": 108, "gap": 573, "edge": 24, "tiny": 12, "unrel": 10, "lowc": 10}[fam]
+
+
+def test_alignment_fixture_keeps_its_undefined_share_and_size():
+    """At most 2 % of the table may be undefined in the reference, and nothing outside the unrelated strings; the fixture stays small."""
+    golden = ac.golden()
+    und = [cid for cid, v in golden.items() if v == ac.UNDEFINED]
+    assert all(ac.family(c) == "unrel" for c in und), und
+    assert 0 < len(und) <= 0.02 * len(golden), (len(und), len(golden))
+    assert os.path.getsize(ac.FIXTURE) < 128 * 1024
+    assert len(golden) >= 773
+
+
+def test_oracle_alignment_of_an_undefined_pair_returns_none():
+    """446 x 151 unrelated bases of this kind made the oracle's traceback index S[-1] (forcex still set at i = 0)."""
+    und = [(s, t) for cid, s, t in ac.by_family("unrel") if ac.golden()[cid] == ac.UNDEFINED]
+    assert und
+    for s, t in und:
+        assert oracle.align(s, t) is None
+    assert oracle.align("C", "ACGT") is None          # the smallest one: T's first base against a gap, then S's only base against a gap
+    assert oracle.align("ACGT", "C") is None          # ... and its mirror image (forcey still set at j = 0)
 
 
 def test_std_hash_known_answers():
