@@ -51,7 +51,9 @@ typedef struct lancet_params {
   int32_t min_report_len;    /* MIN_REPORT_LEN 7             */
   int32_t dist_from_str;     /* DIST_FROM_STR 1              */
   int32_t lr_mode;           /* --linked-reads (LR_MODE false): barcode/haplotype aware coverage   */
-  int32_t reserved;
+  int32_t kmer_recovery;     /* -R / --kmer-recovery (KMER_RECOVERY false): 0 | 1.  After every buildgraph a tumour k-mer seen once lends its
+                                occurrence to the well-supported k-mers one low-quality base away (reference src/ErrorCorrector.hh:38-134,
+                                called at src/Microassembler.cc:137-140).  Not with lr_mode.  (Until this field the slot was `reserved`, 0.) */
   double  min_cov_ratio;     /* MIN_COV_RATIO 0.01           */
 } lancet_params;
 
@@ -147,7 +149,8 @@ typedef struct lancet_engine lancet_engine;
 void lancet_params_default(lancet_params *p);
 
 /* device >= 0 : HIP device ordinal.  There is no CPU backend: creation fails with LANCET_E_NO_DEVICE
- * when no gfx950-compatible device is present.  LANCET_E_UNSUPPORTED: max_k > 127, min_k < 3 or max_unit_len > 8.  Even k is
+ * when no gfx950-compatible device is present.  LANCET_E_UNSUPPORTED: max_k > 127, min_k < 3 or max_unit_len > 8, or kmer_recovery together
+ * with lr_mode (lancet_engine_last_error(NULL) then holds the reason).  LANCET_E_ARG: kmer_recovery other than 0 / 1.  Even k is
  * supported (k-mers that are their own reverse complement: CanonicalMer_t::set ties -> R, reference src/Mer.hh:57-71). */
 int  lancet_engine_create(const lancet_params *p, int device, lancet_engine **out);
 void lancet_engine_destroy(lancet_engine *e);

@@ -7,18 +7,24 @@ from typing import List, Sequence
 import numpy as np
 
 
+class _RecoverySlot(C.Union):
+    """The 16th word of lancet_params: `kmer_recovery`; `reserved` is the name the slot had before (still accepted, same word)."""
+    _fields_ = [("kmer_recovery", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LancetParams(C.Structure):
+    _anonymous_ = ("_slot16",)
     _fields_ = [(n, C.c_int32) for n in (
         "min_k", "max_k", "max_tip_len", "cov_threshold", "low_cov_threshold", "dfs_limit", "max_indel_len",
         "max_mismatch", "min_qual_trim", "min_qual_call", "max_unit_len", "min_report_units", "min_report_len",
-        "dist_from_str", "lr_mode", "reserved")] + [("min_cov_ratio", C.c_double)]
+        "dist_from_str", "lr_mode")] + [("_slot16", _RecoverySlot), ("min_cov_ratio", C.c_double)]
 
 
 def default_params(**over) -> LancetParams:
     """Reference defaults, src/Lancet.hh:33-81."""
     p = LancetParams(min_k=11, max_k=101, max_tip_len=11, cov_threshold=5, low_cov_threshold=1, dfs_limit=1000000,
                      max_indel_len=500, max_mismatch=2, min_qual_trim=10 + 33, min_qual_call=17 + 33,
-                     max_unit_len=4, min_report_units=3, min_report_len=7, dist_from_str=1, lr_mode=0, reserved=0,
+                     max_unit_len=4, min_report_units=3, min_report_len=7, dist_from_str=1, lr_mode=0, kmer_recovery=0,
                      min_cov_ratio=0.01)
     for k, v in over.items():
         setattr(p, k, v)

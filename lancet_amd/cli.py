@@ -8,7 +8,9 @@ Host side (this file, bamio.py, frontend.py): decode the BAMs once, tile the reg
 library or without a device this program stops with an error).  Below it: `lancet_vdb_*` (VariantDB + VCF).
 The VCF is byte-identical to the reference's for the same inputs (tests/test_cli.py, reference-made fixture).
 
-Not offered: --bed, --rg-file, --kmer-recovery, --print-graph (graph dumps), --num-threads (accepted, ignored)."""
+-R / --kmer-recovery as in the reference (lancet_params.kmer_recovery); refused together with --linked-reads before any work is done.
+
+Not offered: --bed, --rg-file, --print-graph (graph dumps), --num-threads (accepted, ignored)."""
 from __future__ import annotations
 
 import argparse
@@ -60,6 +62,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--min-report-len", "-Y", type=int, default=7)
     ap.add_argument("--dist-from-str", "-D", type=int, default=1)
     ap.add_argument("--linked-reads", "-J", action="store_true")
+    ap.add_argument("--kmer-recovery", "-R", action="store_true", help="tumour k-mers seen once lend their occurrence to well-supported k-mers "
+                    "one low-quality base away (reference src/ErrorCorrector.hh); not together with --linked-reads")
     ap.add_argument("--primary-alignment-only", "-I", action="store_true")
     ap.add_argument("--XA-tag-filter", "-O", action="store_true", dest="xa_filter")
     ap.add_argument("--active-region-off", "-W", action="store_true")
@@ -74,13 +78,16 @@ def build_parser() -> argparse.ArgumentParser:
 def run(argv: Optional[List[str]] = None, out=None, date_line: Optional[str] = None) -> int:
     args = build_parser().parse_args(argv)
     out = out or sys.stdout
+    if args.kmer_recovery and args.linked_reads:
+        raise SystemExit("--kmer-recovery (-R) is not supported together with --linked-reads: the linked-read coverages come out of the "
+                         "barcode replay, where recovery is not built")
     qoff = ord(args.quality_range[0])
     params = abi.default_params(
         min_k=args.min_k, max_k=args.max_k, max_tip_len=args.tip_len, cov_threshold=args.cov_thr, low_cov_threshold=args.low_cov,
         dfs_limit=args.dfs_limit, max_indel_len=args.max_indel_len, max_mismatch=args.max_mismatch,
         min_qual_trim=args.trim_lowqual + qoff, min_qual_call=args.min_base_qual + qoff, max_unit_len=args.max_unit_length,
         min_report_units=args.min_report_unit, min_report_len=args.min_report_len, dist_from_str=args.dist_from_str,
-        lr_mode=int(args.linked_reads), min_cov_ratio=args.cov_ratio)
+        lr_mode=int(args.linked_reads), kmer_recovery=int(args.kmer_recovery), min_cov_ratio=args.cov_ratio)
     eng = engine.Engine(params, device=args.device, trace_words=(1 << 17) if args.verbose else 0)     # raises without a GPU
 
     hdr_t, tumor = bamio.read_bam(args.tumor)

@@ -437,6 +437,7 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   LC_GLOBAL uint32_t *clive = (LC_GLOBAL uint32_t *)(area + PRE_OFF_CLIVE);
   LC_GLOBAL uint32_t *cseq = (LC_GLOBAL uint32_t *)(area + PRE_OFF_CSEQ);
   const uint32_t Pn = nsurv + 2u, SRC = nsurv, SNK = nsurv + 1u;
+  const bool recov = lc_sgpr((int)P->kmer_recovery) != 0;                       // -R: X.ord[si] = what the build's recovery pass lent survivor si (Tf | Tr << 16), part of its FLOAT coverage only
   // ---- LDS arena (the reads are done with; pos2si of the component search stays where it is, at byte 70304)
   LC_LDS uint8_t *arena = (LC_LDS uint8_t *)&S.bases[0];
   LC_LDS uint16_t *pos2si = (LC_LDS uint16_t *)(arena + 70304);
@@ -497,7 +498,8 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
     if (e & PB_GONE) continue;
     const uint32_t u = NPOS[e & ON_ID];
     const unsigned long long c4 = TCC[u];
-    const uint32_t tot = (uint32_t)(c4 & 0xFFFFu) + (uint32_t)((c4 >> 16) & 0xFFFFu) + (uint32_t)((c4 >> 32) & 0xFFFFu) + (uint32_t)(c4 >> 48);
+    uint32_t tot = (uint32_t)(c4 & 0xFFFFu) + (uint32_t)((c4 >> 16) & 0xFFFFu) + (uint32_t)((c4 >> 32) & 0xFFFFu) + (uint32_t)(c4 >> 48);
+    if (recov) { const uint32_t rv = X.ord[pos2si[u]]; tot += (rv & 0xFFFFu) + (rv >> 16); }
     if ((float)tot >= (float)P->cov_threshold && !(FL[u] & 32u)) { dev_atomic_min((LC_LDS uint32_t *)&S.g0, (uint32_t)off); dev_atomic_max((LC_LDS uint32_t *)&S.g1, (uint32_t)off + 1u); }      // (kernels.h mark_ref_scan: ... and is in the component)
   }
   WG_SYNC();
@@ -719,7 +721,7 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
     const uint32_t t = HS[cmin] + (onF ? j - 1u : hmF + j - 1u);
     const unsigned long long c4 = TCC[u];
     const uint32_t c0 = (uint32_t)(c4 & 0xFFFFu), c1 = (uint32_t)((c4 >> 16) & 0xFFFFu), c2 = (uint32_t)((c4 >> 32) & 0xFFFFu), c3 = (uint32_t)(c4 >> 48);
-    ORD[t] = c4;
+    ORD[t] = recov ? c4 + (unsigned long long)X.ord[pos2si[u]] : c4;         // (the merge operand is the float coverage: Tf, Tr are the two low fields; mincov below stays on the counts)
     LC_GLOBAL const uint16_t *q0p = qv + ((size_t)ci * K + 0) * 4, *qKp = qv + ((size_t)ci * K + (size_t)(K - 1)) * 4;
     const uint32_t tq0 = (uint32_t)q0p[0] + q0p[1] + q0p[2] + q0p[3], tqK = (uint32_t)qKp[0] + qKp[1] + qKp[2] + qKp[3];
     const uint32_t fl = FL[u] & 3u, hx = HX[cmin];
@@ -1696,6 +1698,77 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
     WG_SYNC();
   }
   const uint32_t nsurv = bl_bcast(&S.nsurv);
+  // ---- -R / --kmer-recovery (ErrorCorrector::mersRecovery, reference src/ErrorCorrector.hh:38-134, called after buildgraph at
+  //      src/Microassembler.cc:137-140; kernels.h build_recover states the rule).  Here the pass runs over the window's occurrences:
+  //      a DONOR's one counted tumour occurrence is a tumour read's occurrence without the overlapping-mate mark whose node is either
+  //      not tracked (one occurrence in all: no per-position counters were ever kept for it, and none are needed -- the positions whose
+  //      tumour quality counter is 0 are the bases of this read below MIN_QUAL_CALL, out of the quality mask in LDS) or tracked with
+  //      tumour counts Tf + Tr == 1.  Only ACCEPTORS that survived the first removeLowCov matter (a node that was removed is not read
+  //      again, and the filter itself does not see the pass: it looks at the per-position counters, and `tumour == 1` is never true of an
+  //      acceptor, before or after): they are found through a table of the survivors' keys in the phase area (the k-mer table is gone),
+  //      and what they receive lands in a per-survivor side counter (Tf | Tr << 16: LDS atomics, exact in any order) that is folded in
+  //      where the float coverages are formed (below), in markRefEnds' scan and in the merge operands of the first compress.
+  const bool recov = lc_sgpr((int)P->kmer_recovery) != 0;
+  if (recov) {
+    LC_GLOBAL const unsigned long long *skey = (LC_GLOBAL const unsigned long long *)(area + PRE_OFF_SKEY);
+    LC_GLOBAL const uint16_t *qv = (LC_GLOBAL const uint16_t *)(area + PRE_OFF_QV);
+    uint32_t hs = 64u; while (hs < nsurv + nsurv / 2u + 2u) hs <<= 1;      // slots: a power of two, at most two thirds full (<= 2 * PB_SCAP)
+    LC_LDS uint32_t *ht = S.big;                                 // [hs] survivor index + 1 (0: empty)
+    LC_LDS uint32_t *rec = S.big + hs;                           // [nsurv]
+    static_assert(4u * (2u * PB_SCAP + PB_SCAP) <= (uint32_t)BL_BIG && PB_SCAP <= 4u * PB_CMAX, "survivor table and counters of the recovery pass");
+    auto key_hash = [&](const BlKm &k) -> uint32_t { unsigned long long h = 0; for (int i = 0; i < BL_KW; ++i) if (i < NW) h = mix64(h ^ (k.w[i] + 0x9e3779b97f4a7c15ULL * (unsigned long long)(i + 1))); return (uint32_t)h; };
+    WG_FOR(i, hs) { ht[i] = 0; }
+    WG_FOR(si, nsurv) { rec[si] = 0; }
+    WG_SYNC();
+    WG_FOR(si, nsurv) {
+      const uint32_t ci = X.s_ci[si];
+      BlKm k; for (int i = 0; i < BL_KW; ++i) k.w[i] = i < NW ? skey[(size_t)ci * PL.kw + (uint32_t)i] : 0ULL;
+      uint32_t sl = key_hash(k) & (hs - 1u);
+      while (dev_atomic_cas32(&ht[sl], 0u, (uint32_t)si + 1u) != 0u) sl = (sl + 1u) & (hs - 1u);      // (distinct keys, a free slot always: ends)
+    }
+    WG_SYNC();
+    bl_for_chunk(S, X.occn, [&](const BlChunk &ch, const BlOccW &w) {
+      const int r = ch.r;
+      if (r == nr) return;                                         // the reference pseudo-read is never counted (Graph.cc:265)
+      const uint32_t ri = S.rinfo[r];
+      if (RI_NML(ri)) return;
+      const uint32_t one = RI_REV(ri) ? (1u << 16) : 1u;           // the donor's strand: that of its one tumour occurrence
+      const uint32_t gw = S.gwo[r];
+      BL_UNROLL for (int j = 0; j < 8; ++j) {
+        if (j >= ch.nv) continue;
+        const uint32_t e = bl_occw_get(w, j);
+        if (e & ON_OVL) continue;                                  // (an overlapping mate's occurrence: counted nowhere)
+        const uint32_t ti = S.cidx[e & ON_ID];
+        if (ti != 0xFFFFu) { const unsigned long long c4 = X.tcc[ti]; if ((uint32_t)(c4 & 0xFFFFu) + (uint32_t)((c4 >> 16) & 0xFFFFu) != 1u) continue; }
+        const int p = ch.p0 + j;
+        if (bl_all_good(S.goodm, gw, p, p + K)) continue;
+        BlKm v0; bl_kmer_x(S.bases, ch.boff0 + (uint32_t)j, NW, K, v0);
+        for (int jb = 0; jb < K; ++jb) {
+          if ((S.goodm[gw + ((uint32_t)(p + jb) >> 5)] >> ((uint32_t)(p + jb) & 31u)) & 1u) continue;
+          for (uint32_t x = 1; x < 4; ++x) {
+            BlKm v, ck, alt; bool isF;
+            for (int i = 0; i < BL_KW; ++i) v.w[i] = v0.w[i] ^ (i == (jb >> 5) ? ((unsigned long long)x << (2 * (jb & 31))) : 0ULL);
+            bl_canon_x(v, NW, K, ck, alt, &isF);                   // (odd k here: no k-mer is its own reverse complement)
+            uint32_t sl = key_hash(ck) & (hs - 1u);
+            for (uint32_t pr = 0; pr < hs; ++pr, sl = (sl + 1u) & (hs - 1u)) {
+              const uint32_t hv = ht[sl];
+              if (hv == 0u) break;
+              const uint32_t si = hv - 1u, ci = X.s_ci[si];
+              bool same = true; for (int i = 0; i < BL_KW; ++i) if (i < NW && skey[(size_t)ci * PL.kw + (uint32_t)i] != ck.w[i]) same = false;
+              if (!same) continue;
+              const unsigned long long c4 = X.tcc[X.c_ti[ci]];
+              LC_GLOBAL const uint16_t *q = qv + ((size_t)ci * K + (size_t)(isF ? jb : K - 1 - jb)) * 4;
+              if ((uint32_t)(c4 & 0xFFFFu) + (uint32_t)((c4 >> 16) & 0xFFFFu) >= 2u && (uint32_t)q[0] + (uint32_t)q[1] > 0u) dev_atomic_add(&rec[si], one);
+              break;
+            }
+          }
+        }
+      }
+    });
+    WG_SYNC();
+    WG_FOR(si, nsurv) { X.ord[si] = rec[si]; }
+    WG_SYNC();
+  }
   BLP(S, 12);
   if (C->debug_stop == 112u) { WG_LANE0 { H->why = 99; } return; }
   // ---- Ref_t::mertable membership, Ref_t::computeCoverage (src/Ref.cc:40-64, 173-250) from the counts of the tracked nodes, the
@@ -1832,11 +1905,12 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
         for (int i = m; i < LC_EMAX; ++i) G.edges[i] = 0;
         const unsigned long long c4 = X.tcc[ti];
         const uint32_t c0 = (uint32_t)(c4 & 0xFFFFu), c1 = (uint32_t)((c4 >> 16) & 0xFFFFu), c2 = (uint32_t)((c4 >> 32) & 0xFFFFu), c3 = (uint32_t)(c4 >> 48);
+        const uint32_t rv = recov ? X.ord[si] : 0u;               // -R: what the tumour singletons lent this k-mer (Tf | Tr << 16)
         const uint32_t f = X.tfl[ti];
         G.flags = f | NF_SURV | ((inmer[n >> 5] >> (n & 31u)) & 1u ? NF_INMER : 0u);
         G.necnt = (uint32_t)m; G.comp = 0; G.color = 0; G.onref = 0; G.nkm = 1;
         G.nkmT = ((f & NF_TUMOR) && !(f & NF_NORMAL)) ? 1u : 0u;
-        G.cov[0] = (float)c0; G.cov[1] = (float)c1; G.cov[2] = (float)c2; G.cov[3] = (float)c3;
+        G.cov[0] = (float)(c0 + (rv & 0xFFFFu)); G.cov[1] = (float)(c1 + (rv >> 16)); G.cov[2] = (float)c2; G.cov[3] = (float)c3;      // (kc: the cov_t counts, which -R leaves alone)
         G.kc[0] = (uint16_t)c0; G.kc[1] = (uint16_t)c1; G.kc[2] = (uint16_t)c2; G.kc[3] = (uint16_t)c3;
         G.mincov = (int)(c0 + c1 + c2 + c3); G.mincovqv = (int)X.c_minqv[ci];
         const uint32_t base = ci * (uint32_t)K;

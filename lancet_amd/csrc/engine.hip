@@ -354,19 +354,28 @@ template <class F> static void lc_parallel(int threads, size_t n, F body) {     
   for (auto &x : th) x.join();
 }
 
+// why the last lancet_engine_create of this thread refused its parameters (there is no engine to ask): lancet_engine_last_error(NULL)
+static std::string &lc_create_err() { static thread_local std::string s; return s; }
+
 extern "C" {
 
 void lancet_params_default(lancet_params *p) {
   memset(p, 0, sizeof(*p));
   p->min_k = 11; p->max_k = 101; p->max_tip_len = 11; p->cov_threshold = 5; p->low_cov_threshold = 1; p->dfs_limit = 1000000;
   p->max_indel_len = 500; p->max_mismatch = 2; p->min_qual_trim = 10 + 33; p->min_qual_call = 17 + 33; p->max_unit_len = 4;
-  p->min_report_units = 3; p->min_report_len = 7; p->dist_from_str = 1; p->lr_mode = 0; p->min_cov_ratio = 0.01;
+  p->min_report_units = 3; p->min_report_len = 7; p->dist_from_str = 1; p->lr_mode = 0; p->kmer_recovery = 0; p->min_cov_ratio = 0.01;
 }
 
 int lancet_engine_create(const lancet_params *p, int device, lancet_engine **out) {
   if (!p || !out) return LANCET_E_ARG;
   *out = nullptr;
+  lc_create_err().clear();
   if (p->max_k > 127 || p->min_k < 3 || p->max_unit_len > 8) return LANCET_E_UNSUPPORTED;
+  if (p->kmer_recovery != 0 && p->kmer_recovery != 1) { lc_create_err() = "kmer_recovery must be 0 or 1"; return LANCET_E_ARG; }
+  if (p->kmer_recovery && p->lr_mode) {      // the linked-read coverages come out of the barcode replay in the window kernel: recovery there is not built
+    lc_create_err() = "kmer_recovery (-R / --kmer-recovery) is not supported together with lr_mode (--linked-reads)";
+    return LANCET_E_UNSUPPORTED;
+  }
   // path_cap (host_common.h lc_caps: max_w + max_indel_len + 256, max_w up to LC_MAXW) must fit the path index of the traceback notes
   if (p->max_indel_len < 0 || (long long)LC_MAXW + (long long)p->max_indel_len + 256 > (long long)LC_NOTE_JMAX) {
     fprintf(stderr, "lancet_engine_create: max_indel_len %d is outside 0..%d (the alignment keeps path positions in 14 bits)\n", (int)p->max_indel_len, LC_NOTE_JMAX - LC_MAXW - 256);
@@ -467,7 +476,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   delete e;
 }
 
-const char *lancet_engine_last_error(const lancet_engine *e) { return e ? e->err.c_str() : "null engine"; }
+const char *lancet_engine_last_error(const lancet_engine *e) { return e ? e->err.c_str() : (lc_create_err().empty() ? "null engine" : lc_create_err().c_str()); }
 
 // debug knob used by the tests: number of 32-bit trace words kept per window (0 = off)
 int lancet_engine_set_trace(lancet_engine *e, uint32_t words_per_window) { if (!e) return LANCET_E_ARG; e->evt_cap = words_per_window; return LANCET_OK; }

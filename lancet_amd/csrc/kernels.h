@@ -2410,6 +2410,70 @@ DEVNI void build_refcov(Ctx &c) {
     WG_SYNC_FENCE();   // from here on the node arrays are only touched with plain loads/stores: one L1 invalidate
   }
 }
+// -R / --kmer-recovery: ErrorCorrector::mersRecovery(nodes_m, 2, MIN_QUAL_CALL), reference src/ErrorCorrector.hh:38-134, run right after
+// buildgraph (src/Microassembler.cc:137-140).  In this table's terms: a DONOR is a node whose counted tumour occurrences are exactly one;
+// that occurrence names a read and an offset, and the positions at which the donor's tumour quality counters are 0 are the bases of that
+// read below MIN_QUAL_CALL (an occurrence that was not counted -- the reference pseudo-read, an overlapping mate -- feeds neither).  One
+// lane per donor: each such base is replaced by the three others in the k-mer as the read has it, the result is made canonical (ties -> R,
+// src/Mer.hh:57-71) and looked up.  The hit is an ACCEPTOR when its tumour count is >= 2 (MIN_SUPPORT, a literal in the reference) and its
+// tumour quality counter is > 0 at the matching position: the read's offset j when the mutated k-mer is canonical as read, K-1-j when its
+// reverse complement is (which of the two the DONOR's key is drops out: the base is the same physical one).  A mutated k-mer that is its own
+// reverse complement (even k) is found by both of the reference's look-ups, once per position.  The acceptor's float tumour coverage on the
+// donor's strand goes up by one; kc[] (the cov_t counts), the quality rows, the reference coverage and the edges stay.  Donors have count 1,
+// acceptors >= 2 and only acceptors change: the pass does not depend on the order of the lanes, and a float that holds a small integer takes
+// +1 exactly.  A hit without quality rows was decided by its count (first removeLowCov): nobody reads its coverage again.
+DEVNI uint32_t kmer_lookup(Ctx &c, const uint8_t *codes, int *ori = nullptr);
+DEV void recover_add(LC_GLOBAL float *f) {
+  LC_GLOBAL uint32_t *w = (LC_GLOBAL uint32_t *)f;
+  uint32_t old = *(volatile LC_GLOBAL uint32_t *)w;
+  while (true) {
+    const uint32_t want = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, old) + 1.0f);
+    const uint32_t got = dev_atomic_cas32(w, old, want);
+    if (got == old) break;
+    old = got;
+  }
+}
+DEVNI void build_recover(Ctx &c) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const int K = S.K, QS = S.QS, Rref = S.R - 1;
+  WG_SYNC_FENCE();                                              // (the records and quality rows of the passes before)
+  XG_FOR(n, S.N) {
+    LC_GLOBAL const NodeGr &G = W.gr[n];
+    if ((uint32_t)G.kc[0] + (uint32_t)G.kc[1] != 1u || (G.flags & NF_NKMER)) continue;
+    const uint32_t lo = W.nocc[n], hi = W.nocc[n + 1];
+    for (uint32_t q = lo; q < hi; ++q) {
+      const cs_t e = W_CSR(W)[q];
+      const int r = (int)CS_READ(e), p = (int)CS_POS(e);
+      if (r == Rref || CS_ST(e) != 0) continue;
+      const lc_u4 rdv = *(const lc_u4 *)(W.rd + 4 * (size_t)r);
+      const uint32_t rinfo = rdv.x, bw = rdv.y, gw = rdv.z;
+      if (RI_NML(rinfo)) continue;
+      const uint32_t strand = RI_REV(rinfo) ? 1u : 0u;          // the donor's strand: where its one tumour occurrence was counted
+      uint8_t codes[LC_NWMAX * 32];
+      for (int j = 0; j < K; ++j) codes[j] = (uint8_t)read_base(c, false, bw, p + j);
+      for (int j = 0; j < K; ++j) {
+        if (rd_good(LC_CTX(c).B->good, gw, p + j)) continue;
+        const uint8_t was = codes[j];
+        for (int x = 1; x < 4; ++x) {
+          codes[j] = (uint8_t)((was + x) & 3);
+          int ori = 0;
+          const uint32_t b = kmer_lookup(c, codes, &ori);
+          if (b == LC_NIL || b == (uint32_t)n) continue;
+          LC_GLOBAL NodeGr &A = W.gr[b];
+          if ((uint32_t)A.kc[0] + (uint32_t)A.kc[1] < 2u || A.nqv == LC_NIL) continue;
+          for (int side = 0; side < 2; ++side) {                // 0: found as read, position j; 1: found reverse-complemented, position K-1-j
+            if (ori != 2 && ori != side) continue;
+            const uint16_t *qq = W.qv + ((size_t)A.nqv * K + (size_t)(side == 0 ? j : K - 1 - j)) * QS;
+            if ((uint32_t)qq[0] + (uint32_t)qq[1] > 0u) recover_add(&A.cov[strand]);
+          }
+        }
+        codes[j] = was;
+      }
+      break;                                                    // (the one counted tumour occurrence)
+    }
+  }
+  WG_SYNC_FENCE();
+}
 DEV void build_graph(Ctx &c) {
   WG_LANE0 { LC_CTX(c).W->qv = LC_CTX(c).W->qv_own; }
   if (!wg_bcast(&LC_SREF(c).items_ready)) { build_items(c); WG_LANE0 { LC_SREF(c).items_ready = 1; } }     // (a window whose graphs all come from the LDS build kernel never needs them)
@@ -2427,6 +2491,7 @@ DEV void build_graph(Ctx &c) {
   build_qcounts(c);
   if (wg_bcast(&LC_SREF(c).overflow)) return;
   build_refcov(c);
+  if (LC_CTX(c).P->kmer_recovery) build_recover(c);               // (wave-uniform; nothing of it is entered without -R)
   STOP_RET(c, 6);
 }
 
@@ -4677,13 +4742,15 @@ DEV void bx_add_node(Ctx &c, uint32_t X, uint32_t nml, uint32_t *n) {
   }
 }
 // node of the k-mer codes[0..K) (2-bit codes) or LC_NIL: the open-addressing table of the current build
-DEVNI uint32_t kmer_lookup(Ctx &c, const uint8_t *codes) {
+// ori (optional): 0 the k-mer is canonical as given, 1 its reverse complement is, 2 it is its own reverse complement (even k; the key is R's)
+DEVNI uint32_t kmer_lookup(Ctx &c, const uint8_t *codes, int *ori) {
   LC_GLOBAL Work &W = *LC_CTX(c).W; LC_WS &S = LC_SREF(c);
   const int K = S.K, NW = S.NW;
   unsigned long long fw[LC_NWMAX], rc[LC_NWMAX];
   for (int w = 0; w < LC_NWMAX; ++w) { fw[w] = 0; rc[w] = 0; }
   for (int i = 0; i < K; ++i) { key_push_fw(fw, NW, K, codes[i] & 3); key_push_rc(rc, NW, K, codes[i] & 3); }
   const unsigned long long *ck = key_less(fw, rc, NW) ? fw : rc;
+  if (ori) *ori = ck == fw ? 0 : (key_less(rc, fw, NW) ? 1 : 2);
   const uint32_t mask = S.tmask;
   unsigned long long h = 0; uint32_t idx;
   if (NW == 1 && K <= 31) { h = ck[0] + 1ULL; idx = (uint32_t)mix64(h) & mask; }
@@ -5637,7 +5704,7 @@ DEVNI bool load_prebuilt(Ctx &c, int k) {
           const uint32_t lo = st > c0 ? st : c0, hi = st + cnt < c1 ? st + cnt : c1;
           if (lo >= hi) continue;                                   // (nothing of this head's slice in the chunk)
           LC_GLOBAL NodeGr &G = W.gr[sid[chl[3 * hx]]];
-          float nc = lo == st ? (float)(uint32_t)G.kc[q] : G.cov[q];
+          float nc = G.cov[q];                                      // (lo == st: still the head's own k-mer's coverage, as the build kernel left it -- its count, plus what -R lent it)
 #ifndef LANCET_WAVE_EMU
           __builtin_amdgcn_s_setprio(3);                            // (a chain of dependent operations: every issue slot it can get)
 #endif

@@ -14,7 +14,8 @@
 // (lancet_records_merge) -- what the reference does with its per-thread databases at the end of main() (reference src/Lancet.cc:940-959).
 // Without --rank the program starts the N ranks itself (children of this process, --rank r --rendezvous <path> appended) and waits for
 // them; a job launcher may start the ranks itself with --rank / --rendezvous.  The VCF (rank 0's stdout) does not depend on N.
-// Not offered: --kmer-recovery, --print-graph; --num-threads is accepted and ignored (windows are
+// -R / --kmer-recovery: lancet_params::kmer_recovery (not together with --linked-reads: refused before any work is done).
+// Not offered: --print-graph; --num-threads is accepted and ignored (windows are
 // batched on the GPU); -v prints the reference's per-window stage trace to stderr.
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
@@ -45,7 +46,7 @@ const Opt OPTS[] = {
   {"min-vaf-tumor", 'e', 1}, {"max-vaf-normal", 'i', 1}, {"min-coverage-tumor", 'o', 1}, {"max-coverage-tumor", 'y', 1},
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
-  {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"primary-alignment-only", 'I', 0},
+  {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
   {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 int die(const std::string &m) { fprintf(stderr, "lancet_gpu: %s\n", m.c_str()); return 1; }
@@ -55,7 +56,9 @@ void usage() {
         "   --window-size, -w  <int>   : at most 1024 bp (the engine's per-window tables; the reference default is 600)\n"
         "   --max-k, -K        <int>   : at most 127; --min-k at least 3; --max-unit-length at most 8\n"
         "   --num-threads, -X  <int>   : accepted and ignored (windows are batched on the GPU)\n"
-        "   --kmer-recovery, --print-graph, --node-str-len, --more-verbose, --print-config-file: not offered\n"
+        "   --kmer-recovery, -R        : as in the reference (tumour k-mers seen once lend their occurrence to well-supported k-mers one\n"
+        "                                low-quality base away); not together with --linked-reads\n"
+        "   --print-graph, --node-str-len, --more-verbose, --print-config-file: not offered\n"
         "Additional options:\n"
         "   --device <n> | --devices a,b,...  : GPU(s) to use; an entry may repeat (two engines on one GPU overlap the upload of a\n"
         "                                       batch with the kernels of the previous one)\n"
@@ -75,7 +78,7 @@ int main(int argc, char **argv) {
   std::string tumor, normal, ref, reg, bed, qrange = "!", date_line, devices, rg_file;
   int min_k = 11, max_k = 101, trim_lowqual = 10, min_base_qual = 17, tip_len = 11, cov_thr = 5, low_cov = 1, dfs_limit = 1000000;
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
-  int device = 0, batch_windows = 8192, verbose = 0, strict = 0, ranks = 0, rank = -1;
+  int device = 0, batch_windows = 8192, verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   std::string rendezvous;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
@@ -104,13 +107,14 @@ int main(int argc, char **argv) {
     else if (L == "min-phred-fisher") flt.min_phred_fisher = atof(v); else if (L == "min-phred-fisher-str") flt.min_phred_fisher_str = atof(v);
     else if (L == "min-strand-bias") flt.min_strand_bias = (int)atof(v); else if (L == "max-unit-length") max_unit_length = atoi(v);
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
-    else if (L == "linked-reads") ho.linked = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
+    else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
     else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
   if (tumor.empty() || normal.empty() || ref.empty() || (reg.empty() && bed.empty())) { usage(); return die("--tumor, --normal, --ref and a region (--reg) or BED file (--bed) are required"); }
+  if (kmer_recovery && ho.linked) return die("--kmer-recovery (-R) is not supported together with --linked-reads: the linked-read coverages come out of the barcode replay, where recovery is not built");
   if (ranks < 0 || (ranks == 0 && rank >= 0) || (ranks > 0 && rank >= ranks)) return die("--ranks must be >= 1 and --rank one of 0 .. ranks-1");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
@@ -154,7 +158,7 @@ int main(int argc, char **argv) {
   P.min_k = min_k; P.max_k = max_k; P.max_tip_len = tip_len; P.cov_threshold = cov_thr; P.low_cov_threshold = low_cov; P.dfs_limit = dfs_limit;
   P.max_indel_len = max_indel_len; P.max_mismatch = max_mismatch; P.min_qual_trim = trim_lowqual + qoff; P.min_qual_call = min_base_qual + qoff;
   P.max_unit_len = max_unit_length; P.min_report_units = min_report_unit; P.min_report_len = min_report_len; P.dist_from_str = dist_from_str;
-  P.lr_mode = ho.linked; P.min_cov_ratio = cov_ratio;
+  P.lr_mode = ho.linked; P.kmer_recovery = kmer_recovery; P.min_cov_ratio = cov_ratio;
   ho.max_k = max_k; ho.min_evidence = flt.min_alt_cnt_tumor; ho.min_qual_call = min_base_qual + qoff;
 
   const bool timing = getenv("LANCET_HOST_TIMING") != nullptr;
