@@ -59,7 +59,8 @@ struct WinShared {
   uint32_t pc_top, pc_rd, pc_base;
   int nitems;                          // work items of the per-occurrence passes (build_items)
   uint32_t part[LANCET_WG + 1];
-  uint32_t part2[LANCET_WG + 1];                 // second scan scratch (part[0..7] carry the path loop's state)
+  uint32_t part2[LANCET_WG + 1];                 // second scan scratch (part[0..7] carry the path loop's state; part2[0..4]: the mismatch positions of
+                                                 // a path that is not aligned, from the Hamming pass to walk_prepare_unaligned)
   int wk[4];                                     // walk_prepare: match / snp / ins / del columns
   int ps_first, ps_len, ps_hd, ps_tl;                 // path_string_wg: first real node, length ; Hamming distance to the reference
   int wk_n;                                      // walk_prepare: number of non-match columns
@@ -4852,6 +4853,36 @@ DEVNI void walk_prepare(Ctx &c, int L) {
   WG_FOR(i, L) { if (F[i + 1] != F[i]) cols[F[i]] = (uint32_t)i; }
   WG_LANE0 { S.wk_n = (int)F[L]; }
 }
+// The same for a path the Hamming test lets through without alignment (equal lengths, 1..LC_HD_MAX mismatches): neither string has a
+// gap, so every column consumes one base of both -- E1[i] = E2[i] = i, the counts are {L - hd, hd, 0, 0} and the column list is the
+// mismatch positions in increasing order.  The Hamming pass left them in S.part2 in the order the lanes met them; lane 0 sorts the
+// handful and writes only the entries the walk reads (E1 / E2 at the listed columns): no scan, no pass over the strings.
+#define LC_HD_MAX 5                              /* reference src/Graph.cc:818-826 */
+DEVNI void walk_prepare_unaligned(Ctx &c, int L, int hd) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  LC_GLOBAL uint32_t *E1 = W.scratch, *E2 = W.scratch + (L + 1), *cols = W.scratch + 3 * (L + 1);
+  WG_LANE0 {
+    for (int a = 1; a < hd; ++a) {
+      const uint32_t v = S.part2[a]; int b = a;
+      for (; b > 0 && S.part2[b - 1] > v; --b) S.part2[b] = S.part2[b - 1];
+      S.part2[b] = v;
+    }
+    for (int a = 0; a < hd; ++a) { const uint32_t i = S.part2[a]; cols[a] = i; E1[i] = i; E2[i] = i; }
+    S.wk[0] = L - hd; S.wk[1] = hd; S.wk[2] = 0; S.wk[3] = 0; S.wk_n = hd;
+  }
+}
+// A path that spells the reference between the anchors (Hamming distance 0): no column differs, so there is no transcript and nothing
+// of the alignment plumbing is needed -- what processPath leaves behind is the path's line of the trace (n matches), the nodes counted
+// as on a reference path, and one more perfect path for eka's summary.
+DEVNI void process_path_perfect_wg(Ctx &c, int np, int n, int complete) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  WG_LANE0 {
+    evt(c, EV_PATH, (uint32_t)complete, (uint32_t)S.tmp3, (uint32_t)n, 0u, 0u, 0u);
+    evt(c, EV_PATH_END);
+    ++S.tmp0;
+  }
+  WG_FOR(i, np) { dev_atomic_add(&W.gr[W.pnodes[i]].onref, 1u); }
+}
 
 // lane 0.  `np` = nodes in path, `plen` = path string length, aligned strings in W.aln (length L).
 DEVNI void process_path_walk(Ctx &c, int np, int plen, int L, int complete) {
@@ -5388,17 +5419,32 @@ DEVNI void count_ref_path(Ctx &c) {
         }
       }
       if (wg_bcastu(&S.part[3]) != 0) break;
+      // the one-lane walk with everything walk_prepare makes, on every path (the emulator's comparison form; tuning builds: --linked-reads windows)
+#ifdef LANCET_WAVE_EMU
+      const bool old_walk = getenv("LANCET_OLD_WALK") != nullptr;
+#elif defined(LANCET_LR_WALK_LANE0)
+      const bool old_walk = wg_uniform(S.LR) != 0;
+#else
+      const bool old_walk = false;
+#endif
+      int hd = -1;
       {
         const int m = replay ? pcache_load(c) : path_string_wg(c, (int)wg_bcastu(&S.part[4]));
-        // Hamming short-cut (reference src/Graph.cc:818-826)
+        // Hamming short-cut (reference src/Graph.cc:818-826); the first mismatch positions are kept for a path that is not aligned
         const int n = wg_bcast(&S.seq_len);
         LC_GLOBAL const uint8_t *rs = LC_CTX(c).B->ref_codes + LC_CTX(c).B->ref_off[S.w] + S.seq_t5;
         WG_LANE0 { S.ps_hd = 0; }
-        if (n == m) { WG_FOR(i, n) { if (rs[i] != W.pseq[i]) dev_atomic_add((LC_LDS uint32_t *)&S.ps_hd, 1u); } }
+        if (n == m) {
+          WG_FOR(i, n) {
+            if (rs[i] != W.pseq[i]) { const uint32_t q = dev_atomic_add((LC_LDS uint32_t *)&S.ps_hd, 1u); if (q < (uint32_t)LC_HD_MAX) S.part2[q] = (uint32_t)i; }
+          }
+        }
         WG_SYNC();
-        const int hd = (n == m) ? wg_uniform(S.ps_hd) : -1;
-        const bool need_align = (hd == -1 || hd > 5);
-        if (!need_align) {
+        hd = (n == m) ? wg_uniform(S.ps_hd) : -1;
+        const bool need_align = (hd == -1 || hd > LC_HD_MAX);
+        // the aligned strings of a path that is not aligned: the two strings themselves (read by the walk at the columns that differ
+        // and copied into the records); a path without a difference needs neither them nor anything else of the walk
+        if (!need_align && (hd > 0 || old_walk)) {
           const int cap = (int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2;
           WG_FOR(i, n) { W.aln[i] = "ACGTN"[rs[i]]; W.aln[cap + i] = "ACGT"[W.pseq[i]]; }
         }
@@ -5421,22 +5467,19 @@ DEVNI void count_ref_path(Ctx &c) {
         align_traceback_fill(c, rs, W.pseq, (int)wg_bcastu(&S.part[7]));
       }
       PHASE(c, 14);
-      SUBPHASE(c, 4, 2);
-      walk_prepare(c, (int)wg_bcastu(&S.part[7]));
-      SUBPHASE(c, 4, 14);
-#ifdef LANCET_WAVE_EMU
-      const bool old_walk = getenv("LANCET_OLD_WALK") != nullptr;      // (emulator only: the one-lane form on every window, to compare the two)
-#else
-      const bool old_walk = false;
-#endif
-#ifdef LANCET_LR_WALK_LANE0                /* (tuning builds: --linked-reads windows on the one-lane walk, as until round 6) */
-      if (old_walk || wg_uniform(S.LR)) {
-#else
-      if (old_walk) {
-#endif
-        WG_LANE0 { if (!S.overflow) process_path_walk(c, (int)S.part[4], (int)S.part[5], (int)S.part[7], (int)S.part[1]); }
-      } else if (!wg_bcast(&S.overflow)) {
-        process_path_walk_wg(c, (int)wg_bcastu(&S.part[4]), (int)wg_bcastu(&S.part[5]), (int)wg_bcastu(&S.part[7]), (int)wg_bcastu(&S.part[1]));
+      if (hd == 0 && !old_walk) {
+        SUBPHASE(c, 4, 7);
+        if (!wg_bcast(&S.overflow)) process_path_perfect_wg(c, (int)wg_bcastu(&S.part[4]), (int)wg_bcastu(&S.part[7]), (int)wg_bcastu(&S.part[1]));
+      } else {
+        SUBPHASE(c, 4, 2);
+        if (hd > 0 && hd <= LC_HD_MAX && !old_walk) walk_prepare_unaligned(c, (int)wg_bcastu(&S.part[7]), hd);
+        else walk_prepare(c, (int)wg_bcastu(&S.part[7]));
+        SUBPHASE(c, 4, 14);
+        if (old_walk) {
+          WG_LANE0 { if (!S.overflow) process_path_walk(c, (int)S.part[4], (int)S.part[5], (int)S.part[7], (int)S.part[1]); }
+        } else if (!wg_bcast(&S.overflow)) {
+          process_path_walk_wg(c, (int)wg_bcastu(&S.part[4]), (int)wg_bcastu(&S.part[5]), (int)wg_bcastu(&S.part[7]), (int)wg_bcastu(&S.part[1]));
+        }
       }
       WG_LANE0 {
         if (!S.overflow) path_flag_edges(c, (int)S.part[4], 1u);
