@@ -421,6 +421,22 @@ DEV void bl_chunk_bases(const LC_LDS uint32_t *bases, int c, unsigned long long 
 #define BLC_TO(e) ((uint32_t)(e) & 0x3FFu)
 #define BLC_DIR(e) (((uint32_t)(e) >> 10) & 3u)
 #define BLC_MAKE(to, dir) ((uint16_t)((to) | ((dir) << 10)))
+// bl_compress_first's graph as a view for cycle_dfs (kernels.h): nodes by position, the edge list of a unitig head in NEWE (found through
+// HS / HX), of any other node in E; colours are bytes, frames 16-bit.  Edges into absorbed k-mers were redirected to their heads before.
+struct CmpGraph {
+  LC_LDS const uint16_t *E, *NEWE, *HX; LC_LDS const uint32_t *HS; LC_LDS const uint8_t *NE, *FL;
+  LC_LDS uint8_t *col; FrameStack<LC_LDS uint16_t *> stk;
+  DEVM EdgeList<LC_LDS const uint16_t *> edges(uint32_t n) const {
+    EdgeList<LC_LDS const uint16_t *> l;
+    if (HS[n + 1] != HS[n]) { l.e = NEWE + 13 * (size_t)HX[n] + 1; l.n = l.e[-1]; } else { l.e = E + 8 * n; l.n = NE[n]; }
+    return l;
+  }
+  DEVM uint32_t e_dir(uint32_t e) const { return BLC_DIR(e); }
+  DEVM uint32_t e_to(uint32_t e) const { return BLC_TO(e); }
+  DEVM bool skipped(uint32_t n) const { return (FL[n] & 12u) != 0; }
+  DEVM uint32_t color(uint32_t n) const { return col[n]; }
+  DEVM void set_color(uint32_t n, uint32_t v) { col[n] = (uint8_t)v; }
+};
 DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const EngineCaps *C, BL_S &S, BlScratch &X, LC_GLOBAL uint8_t *area, const int K_,
                              const uint32_t N_, const uint32_t nsurv_, const uint32_t ncand_, const int reflen_, const uint32_t ht_bc_, const uint32_t refmask_) {
   P = lc_sgpr(P); C = lc_sgpr(C); area = lc_sgpr(area);                        // (uniform arguments: scalar registers, wave.h lc_sgpr)
@@ -833,40 +849,12 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   //      window without a hint; results never depend on what was built ahead.
   WG_LANE0 {
     if (S.hint) {
-      LC_LDS uint8_t *col = INFO;                                                 // (INFO is done with) 0 special / absorbed, 1 unvisited, 2 on the stack, 3 done
-      LC_LDS uint16_t *stk = (LC_LDS uint16_t *)LNK;                              // (the links are done with) frames of (position, next edge, direction)
       static_assert(8 * (PB_CMAX + 2) >= 6 * (PB_CMAX + 3), "DFS stack in the link array");
-      for (uint32_t u = 0; u < Pn; ++u) col[u] = (FL[u] & (12u | 16u)) ? 0 : 1;
-      bool cyc = false;
-      for (int pass = 0; pass < 2 && !cyc; ++pass) {
-        uint32_t sp = 1; stk[0] = (uint16_t)SRC; stk[1] = 0; stk[2] = (uint16_t)(pass == 0 ? 'F' : 'R');
-        col[SRC] = 2;
-        while (sp && !cyc) {
-          LC_LDS uint16_t *fr = stk + 3 * (sp - 1);
-          const uint32_t node = fr[0]; const char dir = (char)fr[2];
-          const bool hd = HS[node + 1] != HS[node];
-          const uint32_t hxn = hd ? (uint32_t)HX[node] : 0u;
-          const uint32_t ne = hd ? (uint32_t)NEWE[13 * (size_t)hxn] : (uint32_t)NE[node];
-          bool descended = false;
-          uint32_t ei = fr[1];
-          while (ei < ne) {
-            const uint32_t e = hd ? NEWE[13 * (size_t)hxn + 1 + ei] : E[8 * node + ei]; ++ei;
-            if (!is_dir(BLC_DIR(e), dir)) continue;
-            const uint32_t other = BLC_TO(e);
-            if (FL[other] & 12u) continue;
-            const uint32_t oc = col[other];
-            if (oc == 2) { cyc = true; break; }
-            if (oc == 1) {
-              col[other] = 2; fr[1] = (uint16_t)ei;
-              LC_LDS uint16_t *nf = stk + 3 * sp; nf[0] = (uint16_t)other; nf[1] = 0; nf[2] = (uint16_t)dir_dest(BLC_DIR(e)); ++sp;
-              descended = true; break;
-            }
-          }
-          if (cyc) break;
-          if (!descended) { col[node] = 3; --sp; }
-        }
-      }
-      if (!cyc) S.hint = 0;
+      CmpGraph v; v.E = E; v.NEWE = NEWE; v.HX = HX; v.HS = HS; v.NE = NE; v.FL = FL;
+      v.col = INFO;                                                               // (INFO is done with) 0 special / absorbed, 1 unvisited, 2 on the stack, 3 done
+      v.stk.st = (LC_LDS uint16_t *)LNK; v.stk.cap = PB_CMAX + 3; v.stk.sp = 0; v.stk.full = false;      // (the links are done with)
+      for (uint32_t u = 0; u < Pn; ++u) v.set_color(u, (FL[u] & (12u | 16u)) ? 0 : 1);
+      if (!cycle_dfs(v, SRC)) S.hint = 0;
     }
   }
   WG_FOR(u, Pn + 1) { AL[u] = ((uint32_t)u < Pn && !(FL[u] & 16u)) ? 1u : 0u; }   // (AL is done with: keep flags by FINAL index)

@@ -855,10 +855,8 @@ DEV void wg_scan(LC_GLOBAL uint32_t *a, int n, LC_WS &S, volatile LC_LDS uint32_
 // node accessors
 // ---------------------------------------------------------------------------------------------------------
 DEV bool n_special(const Ctx &c, uint32_t n) { return (LC_CTX(c).W->gr[n].flags & NF_SPECIAL) != 0; }
-DEV bool n_dead(const Ctx &c, uint32_t n) { return (LC_CTX(c).W->gr[n].flags & NF_DEAD) != 0; }
 DEV int n_len(const Ctx &c, uint32_t n) { return (int)(LC_CTX(c).W->gr[n].seq_hi - LC_CTX(c).W->gr[n].seq_lo); }   // str_m.length()
 DEV int n_strlen(const Ctx &c, uint32_t n) { return n_special(c, n) ? 0 : n_len(c, n); }       // Node_t::strlen
-DEV float n_totcov(const Ctx &c, uint32_t n) { const float *f = LC_CTX(c).W->gr[n].cov; return f[0] + f[1] + f[2] + f[3]; }
 
 DEV int get_buddy(const Ctx &c, uint32_t n, char dir) {             // Node_t::getBuddy, reference src/Node.cc:235-266
   if (n_special(c, n)) return -1;
@@ -1155,7 +1153,6 @@ DEVNI void build_items(Ctx &c) {
       if (pend <= pbeg) continue;
 #define ITEMS_SWEEP(p) for (int _t = 0; _t < _span; ++_t) { const int p = pbeg + _t - _e; if (p < pbeg || p >= pend) continue;
 #define ITEMS_END } } }
-#define ITEMS_END_NOSWEEP } }
 
 template <int NW>
 DEVNI void build_insert_pass(Ctx &c, bool verify) {
@@ -2704,17 +2701,6 @@ DEVNI void compress_node(Ctx &c, uint32_t node, char dir) {          // Graph_t:
 #define CL_VALID 0x80000000u
 #define CL_TO(l) ((l) & 0x0FFFFFFFu)
 #define CL_DIR(l) (((l) >> 28) & 3u)
-DEV uint32_t cmp_link(const Ctx &c, uint32_t n, char dir, bool *irregular) {
-  int uid = get_buddy(c, n, dir);
-  if (uid == -1 || is_tandem(c, n)) return 0u;
-  const uint32_t ew = LC_CTX(c).W->gr[n].edges[uid], edir = ED_DIR(ew), b = ED_TO(ew);
-  if (is_tandem(c, b)) return 0u;
-  const char bdir = (edir == 0 || edir == 2) ? 'R' : 'F';
-  const int buid = get_buddy(c, b, bdir);
-  if (buid == -1) return 0u;
-  if (ED_TO(LC_CTX(c).W->gr[b].edges[buid]) != n) { *irregular = true; return 0u; }
-  return CL_VALID | (edir << 28) | b;
-}
 // First half of a node record (flags, degree, component, colour, the 12 edge words) in registers: the link tests of compress_prepare
 // look at a node's and its neighbours' edges a dozen times each; field by field that was ~100 dependent (L1-hit) loads per node.
 // The loops run over all 12 slots with a predicate, so that the edge words stay in registers (an array indexed at run time would
@@ -3231,26 +3217,6 @@ DEVNI uint32_t compress(Ctx &c, int comp, bool quiet = false) {       // referen
   }
   return clean_dead(c, quiet);
 }
-DEVNI void remove_low_cov(Ctx &c, int comp) {                         // reference src/Graph.cc:2790-2827 (docompression=true)
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  const double avgcov = ((double)S.totalreadbp) / ((double)S.reflen);
-  uint32_t low = 0;
-  for (uint32_t i = 0; i < S.M; ++i) {
-    uint32_t n = W.order[i];
-    if (W.gr[n].comp != comp) continue;
-    if (W.gr[n].flags & NF_SPECIAL) continue;
-    int mq = W.gr[n].mincovqv;
-    float tt = W.gr[n].cov[0] + W.gr[n].cov[1], tn = W.gr[n].cov[2] + W.gr[n].cov[3];
-    if ((mq <= LC_CTX(c).P->low_cov_threshold) || ((double)mq <= (LC_CTX(c).P->min_cov_ratio * avgcov)) || (tt == 1.0f && tn == 1.0f)) { ++low; remove_node(c, n); }
-  }
-  evt(c, EV_LOWCOV, low);
-  clean_dead(c);
-  // Nothing removed: the component was compressed to the end just before (compress is idempotent, hasCycle in between changes
-  // nothing), so the reference's unconditional compress() has nothing to merge -- only its trace lines are owed.
-  if (low == 0) { evt(c, EV_COMPRESS); evt(c, EV_CLEANDEAD, 0); S.tmp2 = 0; }
-  else compress(c, comp);
-  print_stats(c, comp);
-}
 
 // findTandems (reference src/util.cc:574-758) on a code string (0..3): answered from the neighbourhood of `pos` alone; returns ans,
 // len, motif (codes).  The reference scans the whole string and keeps, per unit length and phase, the start of the current
@@ -3335,48 +3301,6 @@ DEV void node_string(const Ctx &c, uint32_t n, LC_GLOBAL uint8_t *out) {      //
   const LC_GLOBAL Work &W = *LC_CTX(c).W;
   uint32_t lo = W.gr[n].seq_lo, hi = W.gr[n].seq_hi;
   for (uint32_t i = lo; i < hi; ++i) out[i - lo] = (uint8_t)SD_BASE(W.seq[i]);
-}
-
-DEVNI void remove_tips(Ctx &c, int comp) {                            // reference src/Graph.cc:2885-2926
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  int tips = 0, round = 0;
-  do {
-    ++round; tips = 0;
-    evt(c, EV_TIPS_ROUND, round);
-    for (uint32_t i = 0; i < S.M; ++i) {
-      uint32_t n = W.order[i];
-      if (W.gr[n].comp != comp) continue;
-      if (W.gr[n].flags & NF_SPECIAL) continue;
-      int deg = (int)W.gr[n].necnt, len = n_strlen(c, n) - S.K + 1;
-      if (deg <= 1 && len < LC_CTX(c).P->max_tip_len) { remove_node(c, n); ++tips; }
-    }
-    evt(c, EV_TIPS_REMOVED, tips);
-    if (tips) compress(c, comp);
-  } while (tips && !S.overflow);
-  print_stats(c, comp);
-}
-DEVNI void remove_short_links(Ctx &c, int comp) {                     // reference src/Graph.cc:2833-2880
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  const double avgcov = ((double)S.totalreadbp) / ((double)S.reflen);
-  const int max_link_len = S.K / 2;                                  // setK: floor(K/2.0)
-  const double thr = floor(sqrt(avgcov));
-  int links = 0;
-  for (uint32_t i = 0; i < S.M; ++i) {
-    uint32_t n = W.order[i];
-    if (W.gr[n].comp != comp) continue;
-    if (W.gr[n].flags & NF_SPECIAL) continue;
-    int deg = (int)W.gr[n].necnt, len = n_len(c, n) - S.K + 1;
-    if (deg >= 2 && len < max_link_len && (double)W.gr[n].mincov <= thr) {
-      int L = 0, ml = 0; uint8_t motif[64];
-      int sl = n_len(c, n);
-      if (sl > (int)LC_CTX(c).C->path_cap) { OVF(c); return; }
-      node_string(c, n, W.pseq);
-      if (!find_tandems_local(c, W.pseq, sl, S.K - 1, &L, motif, &ml)) { remove_node(c, n); ++links; }
-    }
-  }
-  evt(c, EV_LINKS, links);
-  if (links) compress(c, comp);
-  print_stats(c, comp);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3857,51 +3781,16 @@ DEVNI void mark_ref_ends(Ctx &c, int comp) {
   order_insert(c, ins);
 }
 
-DEVNI bool has_cycle(Ctx &c, bool colored = false) {                                         // reference src/Graph.cc:593-681
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  if (S.source == LC_NIL || S.sink == LC_NIL) return false;
-  if (!colored) for (uint32_t i = 0; i < S.M; ++i) { uint32_t n = W.order[i]; if (!(W.gr[n].flags & NF_SPECIAL)) W.gr[n].color = 1; }
-  bool ans = false;
-  // explicit stack of (node, next edge index, dir)
-  LC_GLOBAL uint32_t *st = W.scratch; uint32_t cap = (2 * (LC_CTX(c).C->node_cap + LC_CTX(c).C->special_cap)) / 3;
-  for (int pass = 0; pass < 2 && !ans; ++pass) {
-    uint32_t sp = 0;
-    st[0] = S.source; st[1] = 0; st[2] = (uint32_t)(pass == 0 ? 'F' : 'R'); sp = 1;
-    W.gr[S.source].color = 2;
-    while (sp && !ans) {
-      uint32_t *fr = st + 3 * (sp - 1);
-      uint32_t node = fr[0]; char dir = (char)fr[2];
-      bool descended = false;
-      while (fr[1] < W.gr[node].necnt) {
-        uint32_t e = W.gr[node].edges[fr[1]]; ++fr[1];
-        if (!is_dir(ED_DIR(e), dir)) continue;
-        uint32_t other = ED_TO(e);
-        if (W.gr[other].flags & NF_SPECIAL) continue;
-        if (W.gr[other].color == 2) { ans = true; break; }
-        if (W.gr[other].color == 1) {
-          if (sp >= cap) { OVF(c); return false; }
-          W.gr[other].color = 2;
-          uint32_t *nf = st + 3 * sp; nf[0] = other; nf[1] = 0; nf[2] = (uint32_t)dir_dest(ED_DIR(e)); ++sp;
-          descended = true; break;
-        }
-      }
-      if (ans) break;
-      if (!descended) { W.gr[node].color = 3; --sp; }
-    }
-  }
-  if (ans) evt(c, EV_CYCLE, S.K);
-  return ans;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // The cleaned graph in LDS (round 6).  After the first compress a component is a dozen unitigs, and hasCycle and the path search walk it
 // on one lane: every step a chain of dependent loads from the node records in HBM (flags, degree, an edge word, the neighbour's flags
 // and colour ...), ~35 us per call for a graph that fits a few cache lines.  graph_cache_wg (all lanes) copies what those walks read --
 // per table position: node id, degree, the edges as (position of the neighbour, direction, "used by an earlier path" flag), string
 // length, the special-node bit -- into the staging area of the per-position pass (idle in the graph phases) with an id -> position
-// table beside it; has_cycle_cached / bfs_cached are has_cycle / bfs on that copy: the same visits in the same order.  A table of more
-// than GC_MAX live nodes (or an edge to a node that is not in the table) takes the HBM walk as before.  The copy is made right before
-// each walk: the passes in between rewrite edge lists, and the repeat scan of a path uses the same LDS.
+// table beside it.  The walks themselves exist once, cycle_dfs and path_fifo below, written over a graph view: GcGraph reads this copy,
+// HbmGraph the node records, so the visits and their order are the same by construction.  A table of more than GC_MAX live nodes (or
+// an edge to a node that is not in the table) takes the HBM view as before.  The copy is made right before each walk: the passes in
+// between rewrite edge lists, and the repeat scan of a path uses the same LDS.
 // ---------------------------------------------------------------------------------------------------------
 #define GC_MAX 48
 #define GC_HASH 128
@@ -3962,47 +3851,126 @@ DEVNI bool graph_cache_wg(Ctx &c) {
   }
   return wg_bcast(&S.gc_ok) != 0;
 }
-// has_cycle on the copy (lane 0): colours and the stack of (position, next edge, direction) in LDS too
-DEVNI bool has_cycle_cached(Ctx &c) {
-  LC_WS &S = LC_SREF(c);
-  if (S.source == LC_NIL || S.sink == LC_NIL) return false;
-  volatile LC_LDS uint8_t *base = &S.lbytes[0];
-  const volatile LC_LDS uint32_t *ids = (const volatile LC_LDS uint32_t *)(base + GC_OFF_ID), *hash = (const volatile LC_LDS uint32_t *)(base + GC_OFF_HASH);
-  const volatile LC_LDS uint16_t *ge = (const volatile LC_LDS uint16_t *)(base + GC_OFF_E);
-  const volatile LC_LDS uint8_t *gne = base + GC_OFF_NE, *gfl = base + GC_OFF_FL;
-  volatile LC_LDS uint8_t *col = base + GC_OFF_COL, *st = base + GC_OFF_ST;
-  const int M = (int)S.M;
-  for (int i = 0; i < M; ++i) col[i] = gfl[i] ? 0 : 1;
-  const uint32_t src = gc_lookup(ids, hash, S.source);
-  if (src == LC_NIL) return false;                                  // (the source is in the table whenever it exists)
-  bool ans = false;
-  for (int pass = 0; pass < 2 && !ans; ++pass) {
-    int sp = 0;
-    st[0] = (uint8_t)src; st[1] = 0; st[2] = (uint8_t)(pass == 0 ? 'F' : 'R'); sp = 1;
-    col[src] = 2;
-    while (sp && !ans) {
-      volatile LC_LDS uint8_t *fr = st + 3 * (sp - 1);
-      const uint32_t node = fr[0]; const char dir = (char)fr[2];
+
+// ---------------------------------------------------------------------------------------------------------
+// Graph views.  A view is a small struct of address-space-qualified pointers that answers what the two walks ask of a graph, with
+// nodes named the view's own way (node id in HBM, position in the LDS forms):
+//   edges(n)                          the edge words of node n and how many (EdgeList)
+//   e_dir(e) e_to(e) e_used(e)        an edge word's direction, target, "used by an earlier path" flag
+//   skipped(n)                        hasCycle does not enter n (special; absorbed in the build kernel's form)
+//   color(n) set_color(n, v)          1 unvisited, 2 on the stack, 3 done
+//   stk                               the DFS stack (FrameStack); how wide a frame and a colour are is the view's business
+//   find(id) id(n) strlen(n)          (path search) name of a node id (LC_NIL: not in this view), back, Node_t::strlen
+// ---------------------------------------------------------------------------------------------------------
+template <class P> struct EdgeList { P e; uint32_t n; };
+struct WalkFrame { uint32_t node, next; char dir; };                 // hasCycleRec's state in a node: the node, the next edge to look at, the direction of travel
+template <class P> struct FrameStack {                                // frames of three elements at st, at most cap of them
+  P st; uint32_t cap, sp; bool full;
+  DEVM bool push(uint32_t node, char dir) {
+    if (sp >= cap) { full = true; return false; }
+    st[3 * sp] = node; st[3 * sp + 1] = 0; st[3 * sp + 2] = (uint8_t)dir; ++sp;
+    return true;
+  }
+  DEVM WalkFrame top() const { WalkFrame f; f.node = st[3 * (sp - 1)]; f.next = st[3 * (sp - 1) + 1]; f.dir = (char)st[3 * (sp - 1) + 2]; return f; }
+  DEVM void resume_at(uint32_t next) { st[3 * (sp - 1) + 1] = next; }   // where the top frame goes on once the frame above it is popped
+  DEVM void pop() { --sp; }
+};
+struct HbmGraph {                                                     // the node records; colours in NodeGr::color, 32-bit frames in W.scratch
+  LC_GLOBAL NodeGr *gr; FrameStack<LC_GLOBAL uint32_t *> stk;
+  DEVM EdgeList<LC_GLOBAL const uint32_t *> edges(uint32_t n) const { EdgeList<LC_GLOBAL const uint32_t *> l; l.e = gr[n].edges; l.n = gr[n].necnt; return l; }
+  DEVM uint32_t e_dir(uint32_t e) const { return ED_DIR(e); }
+  DEVM uint32_t e_to(uint32_t e) const { return ED_TO(e); }
+  DEVM uint32_t e_used(uint32_t e) const { return ED_FLAG(e); }
+  DEVM bool skipped(uint32_t n) const { return (gr[n].flags & NF_SPECIAL) != 0; }
+  DEVM uint32_t color(uint32_t n) const { return gr[n].color; }
+  DEVM void set_color(uint32_t n, uint32_t v) { gr[n].color = v; }
+  DEVM uint32_t find(uint32_t id) const { return id; }
+  DEVM uint32_t id(uint32_t n) const { return n; }
+  DEVM int strlen(uint32_t n) const { return skipped(n) ? 0 : (int)(gr[n].seq_hi - gr[n].seq_lo); }
+};
+DEV HbmGraph hbm_graph(const Ctx &c) {
+  HbmGraph v; v.gr = LC_CTX(c).W->gr;
+  v.stk.st = LC_CTX(c).W->scratch; v.stk.cap = (2 * (LC_CTX(c).C->node_cap + LC_CTX(c).C->special_cap)) / 3; v.stk.sp = 0; v.stk.full = false;
+  return v;
+}
+struct GcGraph {                                                      // the copy graph_cache_wg made; colours and frames are bytes behind it
+  const volatile LC_LDS uint32_t *ids, *hash; const volatile LC_LDS uint16_t *ge, *glen; const volatile LC_LDS uint8_t *gne, *gfl;
+  volatile LC_LDS uint8_t *col; FrameStack<volatile LC_LDS uint8_t *> stk;
+  DEVM EdgeList<const volatile LC_LDS uint16_t *> edges(uint32_t n) const { EdgeList<const volatile LC_LDS uint16_t *> l; l.e = ge + 12 * n; l.n = gne[n]; return l; }
+  DEVM uint32_t e_dir(uint32_t e) const { return GC_DIR(e); }
+  DEVM uint32_t e_to(uint32_t e) const { return GC_TPOS(e); }
+  DEVM uint32_t e_used(uint32_t e) const { return GC_FLAG(e); }
+  DEVM bool skipped(uint32_t n) const { return gfl[n] != 0; }
+  DEVM uint32_t color(uint32_t n) const { return col[n]; }
+  DEVM void set_color(uint32_t n, uint32_t v) { col[n] = (uint8_t)v; }
+  DEVM uint32_t find(uint32_t id) const { return gc_lookup(ids, hash, id); }
+  DEVM uint32_t id(uint32_t n) const { return ids[n]; }
+  DEVM int strlen(uint32_t n) const { return (int)glen[n]; }
+};
+DEV GcGraph gc_graph(const Ctx &c) {
+  volatile LC_LDS uint8_t *base = &LC_SREF(c).lbytes[0];
+  GcGraph v;
+  v.ids = (const volatile LC_LDS uint32_t *)(base + GC_OFF_ID); v.hash = (const volatile LC_LDS uint32_t *)(base + GC_OFF_HASH);
+  v.ge = (const volatile LC_LDS uint16_t *)(base + GC_OFF_E); v.glen = (const volatile LC_LDS uint16_t *)(base + GC_OFF_LEN);
+  v.gne = base + GC_OFF_NE; v.gfl = base + GC_OFF_FL; v.col = base + GC_OFF_COL;
+  v.stk.st = base + GC_OFF_ST; v.stk.cap = GC_MAX + 2; v.stk.sp = 0; v.stk.full = false;
+  return v;
+}
+
+// Graph_t::hasCycle's two hasCycleRec calls (reference src/Graph.cc:615-616, 651-681) with an explicit stack: was a node that is on
+// the stack reached from `start`, travelling F, then R?  The colours are the caller's to set up (:605-613).  A stack that is full
+// (HbmGraph alone can be: v.stk.full) ends the walk with false.
+template <class V> DEV bool cycle_dfs(V &v, const uint32_t start) {
+  bool found = false;
+  for (int pass = 0; pass < 2 && !found; ++pass) {
+    v.stk.sp = 0;
+    if (!v.stk.push(start, pass == 0 ? 'F' : 'R')) return false;
+    v.set_color(start, 2);
+    while (v.stk.sp && !found) {
+      const WalkFrame fr = v.stk.top();
+      const auto l = v.edges(fr.node);
       bool descended = false;
-      uint32_t ei = fr[1]; const uint32_t ne = gne[node];
-      while (ei < ne) {
-        const uint32_t e = ge[12 * node + ei]; ++ei;
-        if (!is_dir(GC_DIR(e), dir)) continue;
-        const uint32_t other = GC_TPOS(e);
-        if (gfl[other]) continue;
-        const uint32_t oc = col[other];
-        if (oc == 2) { ans = true; break; }
+      uint32_t ei = fr.next;
+      while (ei < l.n) {
+        const uint32_t e = l.e[ei]; ++ei;
+        if (!is_dir(v.e_dir(e), fr.dir)) continue;
+        const uint32_t other = v.e_to(e);
+        if (v.skipped(other)) continue;
+        const uint32_t oc = v.color(other);
+        if (oc == 2) { found = true; break; }
         if (oc == 1) {
-          col[other] = 2;
-          fr[1] = (uint8_t)ei;
-          volatile LC_LDS uint8_t *nf = st + 3 * sp; nf[0] = (uint8_t)other; nf[1] = 0; nf[2] = (uint8_t)dir_dest(GC_DIR(e)); ++sp;
+          v.stk.resume_at(ei);
+          if (!v.stk.push(other, dir_dest(v.e_dir(e)))) return false;
+          v.set_color(other, 2);
           descended = true; break;
         }
       }
-      if (ans) break;
-      if (!descended) { col[node] = 3; --sp; }
+      if (!found && !descended) { v.set_color(fr.node, 3); v.stk.pop(); }
     }
   }
+  return found;
+}
+// Graph_t::hasCycle (reference src/Graph.cc:593-681) in the window kernel (lane 0): on the node records ...
+DEVNI bool has_cycle(Ctx &c) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  if (S.source == LC_NIL || S.sink == LC_NIL) return false;
+  HbmGraph v = hbm_graph(c);
+  for (uint32_t i = 0; i < S.M; ++i) { const uint32_t n = W.order[i]; if (!v.skipped(n)) v.set_color(n, 1); }
+  const bool ans = cycle_dfs(v, S.source);
+  if (v.stk.full) { OVF(c); return false; }
+  if (ans) evt(c, EV_CYCLE, S.K);
+  return ans;
+}
+// ... and on the copy graph_cache_wg made
+DEVNI bool has_cycle_cached(Ctx &c) {
+  LC_WS &S = LC_SREF(c);
+  if (S.source == LC_NIL || S.sink == LC_NIL) return false;
+  GcGraph v = gc_graph(c);
+  const int M = (int)S.M;
+  for (int i = 0; i < M; ++i) v.set_color((uint32_t)i, v.skipped((uint32_t)i) ? 0 : 1);
+  const uint32_t src = v.find(S.source);
+  if (src == LC_NIL) return false;                                  // (the source is in the table whenever it exists)
+  const bool ans = cycle_dfs(v, src);
   if (ans) evt(c, EV_CYCLE, S.K);
   return ans;
 }
@@ -4010,64 +3978,18 @@ DEVNI bool has_cycle_cached(Ctx &c) {
 // ---------------------------------------------------------------------------------------------------------
 // path enumeration: Graph_t::bfs (reference src/Graph.cc:1299-1425), a FIFO over whole paths.  Paths are
 // queue entries with parent links; the winner is the first-dequeued path with the most unflagged edges.
-// Returns queue index of the best path or LC_NIL.
+// Returns queue index of the best path or LC_NIL.  The queue is in HBM and holds node ids whatever the view:
+// what an expansion reads of the graph comes out of the view.
 // ---------------------------------------------------------------------------------------------------------
 DEV bool path_has_node(const Ctx &c, uint32_t idx, uint32_t node) {
   const BfsEntry *Q = LC_CTX(c).W->queue;
   for (uint32_t i = idx; i != LC_NIL; i = Q[i].parent) if (Q[i].node == node) return true;
   return false;
 }
-DEVNI uint32_t bfs(Ctx &c) {
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  LC_GLOBAL BfsEntry *Q = W.queue;
+template <class V> DEV uint32_t path_fifo(Ctx &c, const V &v) {
+  LC_WS &S = LC_SREF(c);
+  LC_GLOBAL BfsEntry *Q = LC_CTX(c).W->queue;
   const uint32_t cap = LC_CTX(c).C->queue_cap;
-  int reflen = S.seq_len;
-  uint32_t qh = 0, qt = 0;
-  const bool tracing = LC_CTX(c).C->evt_cap != 0;
-  S.bfs_dfs = 0;
-  Q[qt].parent = LC_NIL; Q[qt].node = S.source; Q[qt].edge = LC_NIL; Q[qt].len = S.K; Q[qt].score = 0; Q[qt].dir = 'F'; Q[qt].bits = 1; ++qt;
-  uint32_t best = LC_NIL; int complete = 0; int visit = 0;
-  while (qh < qt) {
-    ++visit;
-    if (LC_CTX(c).P->dfs_limit && visit > LC_CTX(c).P->dfs_limit) { evt(c, EV_DFSLIMIT); S.bfs_dfs = 1; break; }
-    uint32_t idx = qh++;
-    BfsEntry cur = Q[idx];
-    if (cur.node == S.sink && (cur.bits & 1) == 0) {
-      ++complete;
-      if (best == LC_NIL) best = idx; else if (cur.score > Q[best].score) best = idx;
-    } else if (cur.len > reflen + LC_CTX(c).P->max_indel_len) {
-    } else {
-      int cnt = (int)W.gr[cur.node].necnt;
-      for (int i = 0; i < cnt; ++i) {
-        uint32_t e = W.gr[cur.node].edges[i];
-        if (!is_dir(ED_DIR(e), (char)cur.dir)) continue;
-        uint32_t other = ED_TO(e);
-        // Path_t::hasCycle: only ever printed (the -v trace: per path and in the search summary) -- a walk up the whole partial
-        // path per expansion, i.e. quadratic in the path's nodes, so it is evaluated only when the trace is being recorded
-        if (tracing && !(Q[idx].bits & 2) && path_has_node(c, idx, other)) Q[idx].bits |= 2;
-        if (qt >= cap) { OVF(c); return LC_NIL; }
-        BfsEntry ne;
-        ne.parent = idx; ne.node = other; ne.edge = (cur.node << 4) | (uint32_t)i; ne.dir = (uint8_t)dir_dest(ED_DIR(e));
-        ne.len = cur.len + n_strlen(c, other) - S.K + 1;
-        uint32_t ef = ED_FLAG(e);
-        ne.bits = (uint8_t)(((cur.bits & 1) & ef) | (Q[idx].bits & 2));
-        ne.score = (uint16_t)(cur.score + (ef == 0 ? 1 : 0));
-        Q[qt++] = ne;
-      }
-    }
-  }
-  if (complete == 0) best = LC_NIL;
-  return best;
-}
-// bfs on the copy graph_cache_wg made (lane 0): the queue stays where it is, what an expansion reads of the graph comes out of LDS
-DEVNI uint32_t bfs_cached(Ctx &c) {
-  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  LC_GLOBAL BfsEntry *Q = W.queue;
-  const uint32_t cap = LC_CTX(c).C->queue_cap;
-  volatile LC_LDS uint8_t *base = &S.lbytes[0];
-  const volatile LC_LDS uint32_t *ids = (const volatile LC_LDS uint32_t *)(base + GC_OFF_ID), *hash = (const volatile LC_LDS uint32_t *)(base + GC_OFF_HASH);
-  const volatile LC_LDS uint16_t *ge = (const volatile LC_LDS uint16_t *)(base + GC_OFF_E), *glen = (const volatile LC_LDS uint16_t *)(base + GC_OFF_LEN);
-  const volatile LC_LDS uint8_t *gne = base + GC_OFF_NE;
   const int reflen = S.seq_len, K = S.K;
   const int max_indel = LC_CTX(c).P->max_indel_len, dfs_limit = LC_CTX(c).P->dfs_limit;
   const uint32_t sink = S.sink;
@@ -4083,24 +4005,25 @@ DEVNI uint32_t bfs_cached(Ctx &c) {
     const BfsEntry cur = Q[idx];
     if (cur.node == sink && (cur.bits & 1) == 0) {
       ++complete;
-      if (best == LC_NIL || cur.score > best_score) { best = idx; best_score = cur.score; }
+      if (best == LC_NIL || cur.score > best_score) { best = idx; best_score = cur.score; }      // the first dequeued among the highest score
     } else if (cur.len > reflen + max_indel) {
     } else {
-      const uint32_t pos = gc_lookup(ids, hash, cur.node);
-      if (pos == LC_NIL) { OVF(c); return LC_NIL; }                   // (cannot happen: every queue entry's node came out of the table)
-      const int cnt = (int)gne[pos];
+      const uint32_t at = v.find(cur.node);
+      if (at == LC_NIL) { OVF(c); return LC_NIL; }                    // (cannot happen: every queue entry's node came out of the view)
+      const auto l = v.edges(at);
       uint8_t bits2 = cur.bits & 2;
-      for (int i = 0; i < cnt; ++i) {
-        const uint32_t e = ge[12 * pos + (uint32_t)i];
-        if (!is_dir(GC_DIR(e), (char)cur.dir)) continue;
-        const uint32_t tp = GC_TPOS(e), other = ids[tp];
-        // Path_t::hasCycle: only ever printed (see bfs)
+      for (uint32_t i = 0; i < l.n; ++i) {
+        const uint32_t e = l.e[i];
+        if (!is_dir(v.e_dir(e), (char)cur.dir)) continue;
+        const uint32_t to = v.e_to(e), other = v.id(to);
+        // Path_t::hasCycle: only ever printed (the -v trace: per path and in the search summary) -- a walk up the whole partial
+        // path per expansion, i.e. quadratic in the path's nodes, so it is evaluated only when the trace is being recorded
         if (tracing && !bits2 && path_has_node(c, idx, other)) { bits2 = 2; Q[idx].bits |= 2; }
         if (qt >= cap) { OVF(c); return LC_NIL; }
         BfsEntry ne;
-        ne.parent = idx; ne.node = other; ne.edge = (cur.node << 4) | (uint32_t)i; ne.dir = (uint8_t)dir_dest(GC_DIR(e));
-        ne.len = cur.len + (int)glen[tp] - K + 1;
-        const uint32_t ef = GC_FLAG(e);
+        ne.parent = idx; ne.node = other; ne.edge = (cur.node << 4) | i; ne.dir = (uint8_t)dir_dest(v.e_dir(e));
+        ne.len = cur.len + v.strlen(to) - K + 1;
+        const uint32_t ef = v.e_used(e);
         ne.bits = (uint8_t)(((cur.bits & 1) & ef) | bits2);
         ne.score = (uint16_t)(cur.score + (ef == 0 ? 1 : 0));
         Q[qt++] = ne;
@@ -4110,6 +4033,8 @@ DEVNI uint32_t bfs_cached(Ctx &c) {
   if (complete == 0) best = LC_NIL;
   return best;
 }
+DEVNI uint32_t bfs(Ctx &c) { const HbmGraph v = hbm_graph(c); return path_fifo(c, v); }               // (lane 0) on the node records
+DEVNI uint32_t bfs_cached(Ctx &c) { const GcGraph v = gc_graph(c); return path_fifo(c, v); }          // ... on the copy graph_cache_wg made
 // unpack the best path into W.pnodes / W.pedges ; returns number of nodes
 DEVNI int path_unpack(Ctx &c, uint32_t best) {
   LC_GLOBAL Work &W = *LC_CTX(c).W; const BfsEntry *Q = W.queue;
@@ -4234,18 +4159,6 @@ DEVNI int path_string_wg(Ctx &c, int n) {
   }
   WG_SYNC();
   return plen;
-}
-DEV uint32_t path_contig(const Ctx &c, int n, int pos) {            // Path_t::pathcontig, reference src/Path.cc:291-314
-  const LC_GLOBAL Work &W = *LC_CTX(c).W;
-  int cur = 0;
-  for (int i = 0; i < n; ++i) {
-    uint32_t nd = W.pnodes[i];
-    if (W.gr[nd].flags & NF_SPECIAL) continue;
-    int span = n_len(c, nd);
-    if (cur + span >= pos) return nd;
-    cur += span - LC_SREF(c).K + 1;
-  }
-  return LC_NIL;
 }
 DEV bool status_cnt_T(const Ctx &c, uint32_t n) {                   // Node_t::isStatusCnt('T'), reference src/Node.cc:423-440
   double pr = (double)LC_CTX(c).W->gr[n].nkmT / (double)LC_CTX(c).W->gr[n].nkm;

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #define DEV __device__ __forceinline__
 #define DEVNI __device__ __noinline__
+#define DEVM __device__ __forceinline__        /* member function of a small struct of device pointers */
 #ifndef LANCET_FAT
 #define WG_FOR(i, n) for (int i = (int)threadIdx.x; i < (int)(n); i += (int)blockDim.x)
 #define XG_FOR(i, n) WG_FOR(i, n)
@@ -110,6 +111,7 @@ DEV int dev_popcll(unsigned long long x) { return __popcll(x); }
 #include <cmath>
 #define DEV static inline
 #define DEVNI static
+#define DEVM inline
 #define WG_FOR(i, n) for (int i = 0; i < (int)(n); ++i)
 #define LC_ILP 4
 #define LC_ILP_STRIDE 1
