@@ -35,6 +35,7 @@ enum {
   EV_DFSLIMIT, EV_PATH, EV_TS, EV_PATH_END, EV_EKA_END, EV_FOUND, EV_END
 };
 
+struct WalkState { int nts, last_col, code; };   // the transcript walk's column rule (walk_column): its state from one column to the next
 struct WinShared {
   int w, K, NW, R, reflen;
   uint32_t O, N, nspecial, M;          // occurrences, k-mer nodes, special nodes, live order length
@@ -64,7 +65,7 @@ struct WinShared {
   int wk[4];                                     // walk_prepare: match / snp / ins / del columns
   int ps_first, ps_len, ps_hd, ps_tl;                 // path_string_wg: first real node, length ; Hamming distance to the reference
   int wk_n;                                      // walk_prepare: number of non-match columns
-  int wk_stop, wk_nts, wk_last, wk_code, wk_tend, wk_tref;   // process_path_walk_wg: lane 0's state between the chunks of columns
+  int wk_stop, wk_tend, wk_tref; WalkState wk_st;  // process_path_walk_wg: lane 0's state between the rounds of columns (wk_st: the column rule's)
   // (8 KB of LDS per workgroup = 20 single-wave workgroups per CU, the fifth wave per SIMD: two pairs of buffers that are
   //  never live together share their space)
   union alignas(16) {
@@ -4587,6 +4588,8 @@ struct TS {
   // lr_mode, hp0 hp1 hp2: ref minimum and (u16-wrapping) sum per sample ; alt minimum of hpX and of hpX_minqv
   uint16_t hrmnN[3], hrmnT[3], hrsumN[3], hrsumT[3], hamnN[3], hamnT[3], haqN[3], haqT[3];
 };
+constexpr int LC_TS_LDS = (int)(sizeof(WinShared::lbytes) / sizeof(TS));   // transcripts of a path the LDS staging area holds
+struct TSHead { uint32_t pos, ref_pos, start_pos, end_pos, ref_end_pos; int col0, col1; char code, prev_bp_ref, prev_bp_alt; };   // what a record takes of a transcript besides its coverages
 struct HPc { uint16_t nh[3], nq[3], th[3], tq[3]; };   // hp0-2 and hp0-2_minqv of one position, normal / tumor
 template <class T> DEV void ts_hp_init(T &t, const HPc &a, const HPc &r) {
   for (int j = 0; j < 3; ++j) {
@@ -4686,7 +4689,7 @@ DEVNI uint32_t kmer_lookup(Ctx &c, const uint8_t *codes, int *ori) {
   }
   return LC_NIL;
 }
-DEVNI void emit_variant_lr(Ctx &c, uint32_t vi, const TS &t, const uint16_t hp12[12], int plen) {
+DEVNI void emit_variant_lr(Ctx &c, uint32_t vi, const TSHead &t, const uint16_t hp12[12], int plen) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W; DevOut &O = *LC_CTX(c).OUT;
   lancet_variant_lr &l = O.variants_lr[vi];
   for (int q = 0; q < 12; ++q) l.hp[q] = hp12[q];
@@ -4719,7 +4722,7 @@ DEVNI void emit_variant_lr(Ctx &c, uint32_t vi, const TS &t, const uint16_t hp12
   }
 }
 
-DEVNI void emit_variant(Ctx &c, const TS &t, const uint16_t cov[8], int strLen, const uint8_t *motif, int motifLen, bool hasStr,
+DEVNI void emit_variant(Ctx &c, const TSHead &t, const uint16_t cov[8], int strLen, const uint8_t *motif, int motifLen, bool hasStr,
                       const uint8_t *ra, const uint8_t *pa, const uint16_t hp12[12], int plen) {
   LC_WS &S = LC_SREF(c); DevOut &O = *LC_CTX(c).OUT;
   uint32_t vi = dev_atomic_add(O.n_variants, 1u);
@@ -4797,193 +4800,225 @@ DEVNI void process_path_perfect_wg(Ctx &c, int np, int n, int complete) {
   WG_FOR(i, np) { dev_atomic_add(&W.gr[W.pnodes[i]].onref, 1u); }
 }
 
-// lane 0.  `np` = nodes in path, `plen` = path string length, aligned strings in W.aln (length L).
+// ---- The rules of processPath, each stated once.  The two walks below (process_path_walk, process_path_walk_wg) are drivers: they say
+// where a position's values come from, where the transcripts live and how the work is spread over the lanes.  What a column opens,
+// extends or turns complex, and how a finished transcript becomes a record, is decided here and nowhere else.  The functions are
+// templates over the transcript reference (LDS or W.tb) the way acc_* / ts_add_* / ts_hp_* are: the pointer never becomes generic.
+struct WalkPos {              // what one alignment column -- or one of the K + 1 positions behind an indel / complex transcript -- contributes
+  uint16_t cn4[4], ct4[4], rn2[2], rt2[2];     // the path's coverage at P (fwd rev minqv_fwd minqv_rev; normal, tumor), the reference's at its position
+  HPc ha, hr;                                  // the haplotype counts of the two (zeros without --linked-reads)
+  int col, P; uint32_t pos_in_ref; char code;  // column (extension: j), path position, reference position before the column, '^' 'v' 'x'
+  bool tumor, no_spanner, p_outside;           // the spanning node isStatusCnt('T') ; Path_t::pathcontig finds no node ; P is no position of the path
+};
+enum { WALK_GO = 0, WALK_END = 1, WALK_OVF = 2, WALK_FULL = 3 };   // carry on ; the reference's loop ends here ; work-space limit ; staging area full
+DEV WalkState walk_state_load(LC_WS &S) { WalkState st; st.nts = S.wk_st.nts; st.last_col = S.wk_st.last_col; st.code = S.wk_st.code; return st; }
+DEV void walk_state_store(LC_WS &S, const WalkState &st) { S.wk_st.nts = st.nts; S.wk_st.last_col = st.last_col; S.wk_st.code = st.code; }
+DEV void hp_zero(HPc &h) { for (int j = 0; j < 3; ++j) { h.nh[j] = h.th[j] = h.nq[j] = h.tq[j] = 0; } }
+DEV char column_code(uint8_t r, uint8_t p) { return r == '-' ? '^' : (p == '-' ? 'v' : 'x'); }
+// coverage (and haplotype counts) at path position P and reference position refpos, straight from HBM
+DEV void walk_pos_load(Ctx &c, WalkPos &v, int P, uint32_t refpos, int plen, bool lr) {
+  v.P = P; v.p_outside = P < 0 || P >= plen;
+  for (int q = 0; q < 4; ++q) { v.cn4[q] = 0; v.ct4[q] = 0; }
+  hp_zero(v.ha); hp_zero(v.hr);
+  if (!v.p_outside) { path_cov_at(c, P, v.cn4, v.ct4); if (lr) path_hp_at(c, P, v.ha); }
+  ref_cov_at(c, refpos, v.rn2, v.rt2);
+  if (lr) ref_hp_at(c, refpos, v.hr);
+}
+// The column rule (Graph.cc:873-1026): the column extends the last transcript when the column before it is no match, else it opens one.
+//   ra, pa = the aligned strings, rrpos = the column's reference coordinate, cap = transcripts the array holds.
+template <class TP> DEV int walk_column(Ctx &c, TP ts, WalkState &st, int cap, const WalkPos &v, LC_GLOBAL const uint8_t *ra, LC_GLOBAL const uint8_t *pa, unsigned rrpos, bool lr) {
+  const char prev_code = (st.last_col == v.col - 1) ? (char)st.code : '=';       // the column before is a match unless it is the previous listed one
+  const char code = v.code;
+  st.last_col = v.col; st.code = (int)code;
+  if (v.no_spanner) return WALK_END;
+  if (v.p_outside) { OVF(c); return WALK_OVF; }                  // the reference reads coverageN[-1] here (undefined)
+  if (st.nts > 0 && prev_code != '=') {
+    auto &t = ts[st.nts - 1];
+    if (v.tumor) t.somatic = true;
+    const bool del_next = t.pos + (unsigned)(t.col1 - t.col0 + 1) + 1u == rrpos;     // pos + reflen_before + 1: transcript.ref.length() is read after the append
+    t.col1 = v.col; t.end_pos = (uint32_t)v.P; t.ref_end_pos = v.pos_in_ref;
+    if (code == '^' && t.code == code && t.pos == rrpos) { ts_add_alt(t, v.cn4, v.ct4); if (lr) ts_hp_add_alt(t, v.ha); }
+    else if (code == 'v' && t.code == code && del_next) { ts_add_ref(t, v.rn2, v.rt2); if (lr) ts_hp_add_ref(t, v.hr); }
+    else if (code == 'x' || t.code != code) { t.code = 'c'; ts_add_alt(t, v.cn4, v.ct4); ts_add_ref(t, v.rn2, v.rt2); if (lr) { ts_hp_add_alt(t, v.ha); ts_hp_add_ref(t, v.hr); } }
+    return WALK_GO;
+  }
+  // prev_bp: the last A/C/G/T before the column in either string.  Looked for only when a transcript opens: an extension follows a
+  // transcript opened at an earlier column, and opening it found an A/C/G/T before that column in both strings, so it cannot fail there.
+  int pr = v.col - 1, pq = v.col - 1;
+  while (pr >= 0 && ra[pr] != 'A' && ra[pr] != 'C' && ra[pr] != 'G' && ra[pr] != 'T') --pr;
+  while (pq >= 0 && pa[pq] != 'A' && pa[pq] != 'C' && pa[pq] != 'G' && pa[pq] != 'T') --pq;
+  if (pr < 0 || pq < 0) { OVF(c); return WALK_OVF; }             // reference: assert(pr >= 0)
+  if (st.nts >= LC_MAXTS) { OVF(c); return WALK_OVF; }
+  if (st.nts >= cap) return WALK_FULL;
+  auto &t = ts[st.nts++];
+  t.pos = rrpos; t.ref_pos = v.pos_in_ref; t.start_pos = (uint32_t)(v.P + 1); t.code = code; t.end_pos = (uint32_t)v.P; t.ref_end_pos = v.pos_in_ref;
+  t.col0 = v.col; t.col1 = v.col; t.somatic = v.tumor; t.prev_bp_ref = (char)ra[pr]; t.prev_bp_alt = (char)pa[pq];
+  for (int q = 0; q < 4; ++q) { acc_init(t.aN[q], v.cn4[q]); acc_init(t.aT[q], v.ct4[q]); }
+  for (int q = 0; q < 2; ++q) { acc_init(t.rN[q], v.rn2[q]); acc_init(t.rT[q], v.rt2[q]); }
+  ts_hp_init(t, v.ha, v.hr);                                     // (zeros without --linked-reads)
+  return WALK_GO;
+}
+// The extension step (Graph.cc:1036-1068): one of the K + 1 positions behind an indel / complex transcript.  A position past the path's
+// end (p_outside) contributes the reference's side only.  false: no node spans the position, the reference leaves its loop over j.
+template <class T> DEV bool walk_extend(T &t, const WalkPos &v, bool lr) {
+  if (!v.p_outside) {
+    if (v.no_spanner) return false;
+    if (v.tumor) t.somatic = true;
+    ts_add_alt(t, v.cn4, v.ct4); if (lr) ts_hp_add_alt(t, v.ha);
+  }
+  ts_add_ref(t, v.rn2, v.rt2); if (lr) ts_hp_add_ref(t, v.hr);
+  return true;
+}
+// The coverages of a transcript's record: RCNF RCNR RCTF RCTR ACNF ACNR ACTF ACTR, and HPRN HPRT HPAN HPAT as {hp1, hp2, hp0}
+// (Graph.cc:1091-1128, 1166-1169: minima of the ref / alt counts, means of the ref counts when somatic; zeros without --linked-reads)
+template <class T> DEV void ts_record_cov(const T &t, bool lr, uint16_t cov[8], uint16_t hp12[12]) {
+  const bool x = t.code == 'x';
+  uint16_t RCNF = t.rN[0].mn, RCNR = t.rN[1].mn, RCTF = t.rT[0].mn, RCTR = t.rT[1].mn;
+  uint16_t ACNF = x ? t.aN[2].mn : t.aN[0].mnz, ACNR = x ? t.aN[3].mn : t.aN[1].mnz;      // getMinNon0Cov*: code != 'x' -> .fwd/.rev
+  const uint16_t ACTF = x ? t.aT[2].mn : t.aT[0].mn, ACTR = x ? t.aT[3].mn : t.aT[1].mn;
+  if (t.somatic) { RCNF = acc_mean(t.rN[0]); RCNR = acc_mean(t.rN[1]); RCTF = acc_mean(t.rT[0]); RCTR = acc_mean(t.rT[1]); ACNF = 0; ACNR = 0; }
+  const uint16_t cv[8] = {RCNF, RCNR, RCTF, RCTR, ACNF, ACNR, ACTF, ACTR};
+  for (int q = 0; q < 8; ++q) cov[q] = cv[q];
+  for (int q = 0; q < 12; ++q) hp12[q] = 0;
+  if (!lr) return;
+  const uint32_t nref = t.rN[0].n;
+  auto mean = [&](uint16_t sum) -> uint16_t { return nref > 0 ? (uint16_t)((float)sum / (float)nref) : (uint16_t)0; };
+  for (int j = 0; j < 3; ++j) {
+    const int q = (j + 2) % 3;                                   // hp1, hp2, hp0
+    hp12[q] = t.somatic ? mean(t.hrsumN[j]) : t.hrmnN[j]; hp12[3 + q] = t.somatic ? mean(t.hrsumT[j]) : t.hrmnT[j];
+    hp12[6 + q] = t.somatic ? (uint16_t)0 : (x ? t.haqN[j] : t.hamnN[j]); hp12[9 + q] = x ? t.haqT[j] : t.hamnT[j];
+  }
+}
+// The transcript's record: its line of the trace, and -- when the alternative allele has coverage -- findTandems and the variant.
+// stg: the path string around the transcript in LDS (find_tandems_local), when the caller staged it.
+template <class T> DEV void walk_record(Ctx &c, const T &t, LC_GLOBAL const uint8_t *ra, LC_GLOBAL const uint8_t *pa, int plen, bool lr,
+                                        const volatile LC_LDS uint8_t *stg = nullptr, int stg_lo = 0, int stg_hi = 0) {
+  uint16_t cov[8], hp12[12];
+  ts_record_cov(t, lr, cov, hp12);
+  TSHead h;                                                      // (what emit_variant reads, out of LDS or W.tb)
+  h.pos = t.pos; h.ref_pos = t.ref_pos; h.start_pos = t.start_pos; h.end_pos = t.end_pos; h.ref_end_pos = t.ref_end_pos; h.col0 = t.col0; h.col1 = t.col1;
+  h.code = t.code; h.prev_bp_ref = t.prev_bp_ref; h.prev_bp_alt = t.prev_bp_alt;
+  const uint32_t rl = (uint32_t)(h.col1 - h.col0 + 1);
+  if (LC_CTX(c).C->evt_cap) {
+    evt(c, EV_TS, h.pos, rl, ((uint32_t)cov[0] << 16) | cov[1], ((uint32_t)cov[2] << 16) | cov[3], ((uint32_t)cov[4] << 16) | cov[5], ((uint32_t)cov[6] << 16) | cov[7],
+        ((uint32_t)(uint8_t)h.prev_bp_ref << 8) | (uint8_t)h.prev_bp_alt);
+    evt_bytes(c, ra + h.col0, rl);
+    evt_bytes(c, pa + h.col0, rl);
+    evt_bytes(c, (const uint8_t *)hp12, 24);
+  }
+  if (cov[4] > 0 || cov[5] > 0 || cov[6] > 0 || cov[7] > 0) {
+    int LEN = 0, ml = 0; uint8_t motif[64];
+    const bool ans = find_tandems_local(c, LC_CTX(c).W->pseq, plen, (int)h.start_pos, &LEN, motif, &ml, stg, stg_lo, stg_hi);
+    emit_variant(c, h, cov, LEN, motif, ml, ans, ra, pa, hp12, plen);
+  }
+}
+// the path's class for eka's summary: the counters (perfect / withsnps / withindel / withmix) ride in tmp0..tmp2 + part[0]
+DEV void eka_count(LC_WS &S) {
+  const int snp_bp = S.wk[1], ins_bp = S.wk[2], del_bp = S.wk[3];
+  if ((snp_bp + ins_bp + del_bp) == 0) ++S.tmp0; else if (snp_bp == 0) ++S.tmp1; else if ((ins_bp + del_bp) == 0) ++S.tmp2; else ++S.part[0];
+}
+
+// The one-lane driver (lane 0): every value straight from HBM, the transcripts in W.tb.  Taken when the path's node table or descriptors
+// do not fit the whole-wave driver's tables, when a path has more transcripts than the LDS staging area holds (from the start again),
+// and as the emulator's comparison form (LANCET_OLD_WALK).  `np` = nodes in path, `plen` = path string length, aligned strings in W.aln (length L).
 DEVNI void process_path_walk(Ctx &c, int np, int plen, int L, int complete) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
-  const int K = S.K;
+  const int K = S.K, trim5 = S.trim5;
+  const bool LR = S.LR != 0;
   const int cap = (int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2;
   LC_GLOBAL const uint8_t *ra = W.aln, *pa = W.aln + cap;
   const int refstart = LC_CTX(c).B->ref_start[S.w];
   TS *ts = (TS *)(void *)W.tb;                 // the traceback matrix is dead by now: reuse it for the transcripts
-  auto ts_at = [&](int idx) -> TS & { return ts[idx]; };
-  int nts = 0;
-  unsigned pos_in_ref = 0, pathpos = 0;
-  char code = '?', prev_code = '?';
-  const int match_bp = S.wk[0], snp_bp = S.wk[1], ins_bp = S.wk[2], del_bp = S.wk[3];      // walk_prepare
   LC_GLOBAL const uint32_t *E1 = W.scratch, *E2 = W.scratch + (L + 1), *cols = W.scratch + 3 * (L + 1);
-  int pc_i = 0, pc_cur = 0;
-  int last_col = -2;
-  for (int ci = 0; ci < S.wk_n; ++ci) {
-    const int i = (int)cols[ci];
-    prev_code = (last_col == i - 1) ? code : '=';       // the column before is a match unless it is the previous listed one
-    last_col = i;
-    if (ra[i] == '-') code = '^'; else if (pa[i] == '-') code = 'v'; else code = 'x';
-    pos_in_ref = E1[i];
-    pathpos = E2[i] + (pa[i] != '-' ? 1u : 0u);
-    // Path_t::pathcontig(pathpos): pathpos never decreases, so the scan over the path's nodes resumes where it stopped
-    uint32_t spanner = LC_NIL;
-    for (; pc_i < np; ++pc_i) {
-      const uint32_t nd = W.pnodes[pc_i];
-      if (W.gr[nd].flags & NF_SPECIAL) continue;
-      const int span = n_len(c, nd);
-      if (pc_cur + span >= (int)pathpos) { spanner = nd; break; }
-      pc_cur += span - K + 1;
-    }
-    if (spanner == LC_NIL) break;
-    bool within_tumor = status_cnt_T(c, spanner);
-    int P = (int)pathpos - 1;
-    if (P < 0 || P >= plen) { OVF(c); return; }      // the reference reads coverageN[-1] here (undefined)
-    {
-      uint16_t cn4[4], ct4[4], rn2[2], rt2[2];
-      path_cov_at(c, P, cn4, ct4);
-      ref_cov_at(c, pos_in_ref + (uint32_t)S.trim5, rn2, rt2);
-      HPc ha, hr;
-      path_hp_at(c, P, ha);
-      ref_hp_at(c, pos_in_ref + (uint32_t)S.trim5, hr);
-      unsigned rrpos = pos_in_ref + (unsigned)refstart + (unsigned)S.trim5;
-      int pr = i - 1, pq = i - 1;
-      while (pr >= 0 && ra[pr] != 'A' && ra[pr] != 'C' && ra[pr] != 'G' && ra[pr] != 'T') --pr;
-      while (pq >= 0 && pa[pq] != 'A' && pa[pq] != 'C' && pa[pq] != 'G' && pa[pq] != 'T') --pq;
-      if (pr < 0 || pq < 0) { OVF(c); return; }        // reference: assert(pr >= 0)
-      if (nts > 0 && prev_code != '=') {
-        TS &t = ts_at(nts - 1);
-        if (within_tumor) t.somatic = true;
-        int reflen_before = t.col1 - t.col0 + 1;        // transcript.ref.length() before the append
-        t.col1 = i; t.end_pos = (uint32_t)P; t.ref_end_pos = pos_in_ref;
-        if (code == '^' && t.code == code && t.pos == rrpos) { ts_add_alt(t, cn4, ct4); ts_hp_add_alt(t, ha); }
-        else if (code == 'v' && t.code == code && (t.pos + (unsigned)(reflen_before + 1)) == rrpos) { ts_add_ref(t, rn2, rt2); ts_hp_add_ref(t, hr); }
-        else if (code == 'x' || t.code != code) { t.code = 'c'; ts_add_alt(t, cn4, ct4); ts_add_ref(t, rn2, rt2); ts_hp_add_alt(t, ha); ts_hp_add_ref(t, hr); }
-      } else {
-        if (nts >= LC_MAXTS) { OVF(c); return; }
-        TS &t = ts_at(nts++);
-        t.pos = rrpos; t.ref_pos = pos_in_ref; t.start_pos = (uint32_t)(P + 1); t.code = code; t.end_pos = (uint32_t)P; t.ref_end_pos = pos_in_ref;
-        t.col0 = i; t.col1 = i; t.somatic = within_tumor; t.prev_bp_ref = (char)ra[pr]; t.prev_bp_alt = (char)pa[pq];
-        for (int q = 0; q < 4; ++q) { acc_init(t.aN[q], cn4[q]); acc_init(t.aT[q], ct4[q]); }
-        for (int q = 0; q < 2; ++q) { acc_init(t.rN[q], rn2[q]); acc_init(t.rT[q], rt2[q]); }
-        ts_hp_init(t, ha, hr);
-      }
-    }
-  }
-  // bit 1 of the BFS entry = Path_t::hasCycle_m
-  evt(c, EV_PATH, (uint32_t)complete, (uint32_t)S.tmp3, (uint32_t)match_bp, (uint32_t)snp_bp, (uint32_t)ins_bp, (uint32_t)del_bp);
   // Path_t::pathcontig over positions that mostly increase: the scan over the path's nodes resumes where the last one stopped
   // (from the start again when a position lies before the last one) instead of walking the path from its first node per position
   int ct_i = 0, ct_cur = 0, ct_last = -1;
-  auto contig_at = [&](int pos) -> uint32_t {
-    if (pos < ct_last) { ct_i = 0; ct_cur = 0; }
-    ct_last = pos;
+  auto pos_at = [&](WalkPos &v, int pathpos, int P, uint32_t refpos) {
+    if (pathpos < ct_last) { ct_i = 0; ct_cur = 0; }
+    ct_last = pathpos;
+    uint32_t spanner = LC_NIL;
     for (; ct_i < np; ++ct_i) {
       const uint32_t nd = W.pnodes[ct_i];
       if (W.gr[nd].flags & NF_SPECIAL) continue;
       const int span = n_len(c, nd);
-      if (ct_cur + span >= pos) return nd;
+      if (ct_cur + span >= pathpos) { spanner = nd; break; }
       ct_cur += span - K + 1;
     }
-    return LC_NIL;
+    v.no_spanner = spanner == LC_NIL; v.tumor = !v.no_spanner && status_cnt_T(c, spanner);
+    walk_pos_load(c, v, P, refpos, plen, LR);
   };
-  for (int ti = 0; ti < nts; ++ti) {
-    TS &t = ts_at(ti);
+  WalkState st = {0, -2, '?'};
+  for (int ci = 0; ci < S.wk_n; ++ci) {
+    WalkPos v;
+    v.col = (int)cols[ci]; v.code = column_code(ra[v.col], pa[v.col]); v.pos_in_ref = E1[v.col];
+    const int pathpos = (int)(E2[v.col] + (pa[v.col] != '-' ? 1u : 0u));
+    pos_at(v, pathpos, pathpos - 1, v.pos_in_ref + (uint32_t)trim5);
+    const int r = walk_column(c, ts, st, LC_MAXTS, v, ra, pa, v.pos_in_ref + (unsigned)refstart + (unsigned)trim5, LR);
+    if (r == WALK_END) break;
+    if (r != WALK_GO) return;
+  }
+  // bit 1 of the BFS entry = Path_t::hasCycle_m
+  evt(c, EV_PATH, (uint32_t)complete, (uint32_t)S.tmp3, (uint32_t)S.wk[0], (uint32_t)S.wk[1], (uint32_t)S.wk[2], (uint32_t)S.wk[3]);
+  for (int ti = 0; ti < st.nts; ++ti) {
+    TS &t = ts[ti];
     if (t.code != 'x') {
       for (int j = 0; j <= K; ++j) {
-        unsigned idx1 = t.end_pos + (unsigned)j;
-        if (idx1 < (unsigned)plen) {
-          uint32_t sp = contig_at((int)idx1);
-          if (sp == LC_NIL) break;
-          if (status_cnt_T(c, sp)) t.somatic = true;
-          uint16_t cn4[4], ct4[4];
-          path_cov_at(c, (int)idx1, cn4, ct4);
-          ts_add_alt(t, cn4, ct4);
-          if (S.LR) { HPc ha; path_hp_at(c, (int)idx1, ha); ts_hp_add_alt(t, ha); }
-        }
-        unsigned idx2 = t.ref_end_pos + (unsigned)S.trim5 + (unsigned)j;
-        uint16_t rn2[2], rt2[2];
-        ref_cov_at(c, idx2, rn2, rt2);
-        ts_add_ref(t, rn2, rt2);
-        if (S.LR) { HPc hr; ref_hp_at(c, idx2, hr); ts_hp_add_ref(t, hr); }
+        const unsigned idx1 = t.end_pos + (unsigned)j;
+        WalkPos v;
+        pos_at(v, (int)idx1, idx1 < (unsigned)plen ? (int)idx1 : -1, t.ref_end_pos + (uint32_t)trim5 + (uint32_t)j);
+        if (!walk_extend(t, v, LR)) break;
       }
     }
-    bool x = t.code == 'x';
-    uint16_t RCNF = t.rN[0].mn, RCNR = t.rN[1].mn, RCTF = t.rT[0].mn, RCTR = t.rT[1].mn;
-    uint16_t ACNF = x ? t.aN[2].mn : t.aN[0].mn, ACNR = x ? t.aN[3].mn : t.aN[1].mn;
-    if (!x) { ACNF = t.aN[0].mnz; ACNR = t.aN[1].mnz; }     // getMinNon0Cov*: code != 'x' -> .fwd/.rev
-    uint16_t ACTF = x ? t.aT[2].mn : t.aT[0].mn, ACTR = x ? t.aT[3].mn : t.aT[1].mn;
-    if (t.somatic) { RCNF = acc_mean(t.rN[0]); RCNR = acc_mean(t.rN[1]); RCTF = acc_mean(t.rT[0]); RCTR = acc_mean(t.rT[1]); ACNF = 0; ACNR = 0; }
-    uint16_t cov[8] = {RCNF, RCNR, RCTF, RCTR, ACNF, ACNR, ACTF, ACTR};
-    // haplotype counts (Graph.cc:1091-1128): min of the ref / alt counts, means of the ref counts when somatic
-    uint16_t hp12[12];                                  // HPRN HPRT HPAN HPAT as {hp1, hp2, hp0} (Graph.cc:1166-1169)
-    {
-      const uint32_t nref = t.rN[0].n;
-      auto mean = [&](uint16_t sum) -> uint16_t { return nref > 0 ? (uint16_t)((float)sum / (float)nref) : (uint16_t)0; };
-      uint16_t RN[3], RT[3], AN[3], AT[3];
-      for (int j = 0; j < 3; ++j) {
-        RN[j] = t.hrmnN[j]; RT[j] = t.hrmnT[j];
-        AN[j] = x ? t.haqN[j] : t.hamnN[j]; AT[j] = x ? t.haqT[j] : t.hamnT[j];
-        if (t.somatic) { RT[j] = mean(t.hrsumT[j]); RN[j] = mean(t.hrsumN[j]); AN[j] = 0; }
-        if (!S.LR) { RN[j] = RT[j] = AN[j] = AT[j] = 0; }
-      }
-      const uint16_t v[12] = {RN[1], RN[2], RN[0], RT[1], RT[2], RT[0], AN[1], AN[2], AN[0], AT[1], AT[2], AT[0]};
-      for (int q = 0; q < 12; ++q) hp12[q] = v[q];
-    }
-    if (LC_CTX(c).C->evt_cap) {
-      evt(c, EV_TS, t.pos, (uint32_t)(t.col1 - t.col0 + 1), ((uint32_t)RCNF << 16) | RCNR, ((uint32_t)RCTF << 16) | RCTR,
-          ((uint32_t)ACNF << 16) | ACNR, ((uint32_t)ACTF << 16) | ACTR, ((uint32_t)(uint8_t)t.prev_bp_ref << 8) | (uint8_t)t.prev_bp_alt);
-      evt_bytes(c, ra + t.col0, (uint32_t)(t.col1 - t.col0 + 1));
-      evt_bytes(c, pa + t.col0, (uint32_t)(t.col1 - t.col0 + 1));
-      evt_bytes(c, (const uint8_t *)hp12, 24);
-    }
-    if (ACNF > 0 || ACNR > 0 || ACTF > 0 || ACTR > 0) {
-      int LEN = 0, ml = 0; uint8_t motif[64];
-      bool ans = find_tandems_local(c, W.pseq, plen, (int)t.start_pos, &LEN, motif, &ml);
-      emit_variant(c, t, cov, LEN, motif, ml, ans, ra, pa, hp12, plen);
-    }
+    walk_record(c, t, ra, pa, plen, LR);
   }
   evt(c, EV_PATH_END);
   for (int i = 0; i < np; ++i) ++W.gr[W.pnodes[i]].onref;
-  // counters of eka (perfect / withsnps / withindel / withmix) ride in tmp0..tmp2 + part[0]
-  if ((snp_bp + ins_bp + del_bp) == 0) ++S.tmp0; else if (snp_bp == 0) ++S.tmp1; else if ((ins_bp + del_bp) == 0) ++S.tmp2; else ++S.part[0];
+  eka_count(S);
 }
 
-// The same walk with the looking-up done by all lanes (short reads; --linked-reads keeps the one-lane form above).
-// What a column contributes -- the path's and the reference's coverage at its position, the node that spans it -- does not
-// depend on the columns before it, and in HBM it is a chain of ~15 dependent loads per column (and per position of the K+1
-// positions every indel is extended by), which made this the longest phase of the windows that align.  So: the lanes gather
-// 64 columns at a time into LDS records (the `acc` area of the build phases, idle here), lane 0 then runs the reference's
-// sequential rules (which transcript a column opens / extends / turns complex) over LDS.  Path_t::pathcontig becomes a
-// binary search over the path's node ends (they grow along the path).
+// The whole-wave driver (production).  What a column contributes -- the path's and the reference's coverage at its position, the node
+// that spans it -- does not depend on the columns before it, and in HBM it is a chain of ~15 dependent loads per column (and per
+// position of the K+1 positions every indel is extended by), which made this the longest phase of the windows that align.  So: the
+// lanes gather 64 columns at a time into LDS records (the `acc` area of the build phases, idle here), lane 0 then runs the
+// reference's sequential rules above over LDS.  Path_t::pathcontig becomes a binary search over the path's node ends (they grow
+// along the path).  --linked-reads takes the same form with 32 columns per round and 19-word records.
 //   record (10 words): alt N fwd|rev, N qf|qr, alt T fwd|rev, T qf|qr, ref N fwd|rev, ref T fwd|rev, column / position j, P, pos_in_ref,
 //                      flags (1 spanner within tumor, 2 no spanner, 4 P outside the path) | column code << 8
 // (lr: words 10..18 of the record take the haplotype counts of the position too -- path hp0-2 and hp0-2_minqv, normal then tumor; reference hp0-2)
-DEV void walk_gather(Ctx &c, volatile LC_LDS uint32_t *rec, int pathpos, int P, uint32_t refpos, int plen, int np, LC_GLOBAL const uint32_t *pend, uint32_t w6, uint32_t w8, uint32_t code, bool lr = false) {
-  LC_GLOBAL Work &W = *LC_CTX(c).W;
-  uint32_t fl = 0;
+DEV uint32_t pk16(uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); }
+DEV void walk_pack(volatile LC_LDS uint32_t *rec, const WalkPos &v, bool lr) {
+  rec[0] = pk16(v.cn4[0], v.cn4[1]); rec[1] = pk16(v.cn4[2], v.cn4[3]); rec[2] = pk16(v.ct4[0], v.ct4[1]); rec[3] = pk16(v.ct4[2], v.ct4[3]);
+  rec[4] = pk16(v.rn2[0], v.rn2[1]); rec[5] = pk16(v.rt2[0], v.rt2[1]);
+  rec[6] = (uint32_t)v.col; rec[7] = (uint32_t)v.P; rec[8] = v.pos_in_ref;
+  rec[9] = (v.tumor ? 1u : 0u) | (v.no_spanner ? 2u : 0u) | (v.p_outside ? 4u : 0u) | ((uint32_t)(uint8_t)v.code << 8);
+  if (lr) {
+    uint16_t h[18];
+    for (int j = 0; j < 3; ++j) { h[j] = v.ha.nh[j]; h[3 + j] = v.ha.nq[j]; h[6 + j] = v.ha.th[j]; h[9 + j] = v.ha.tq[j]; h[12 + j] = v.hr.nh[j]; h[15 + j] = v.hr.th[j]; }
+    for (int q = 0; q < 9; ++q) rec[10 + q] = pk16(h[2 * q], h[2 * q + 1]);
+  }
+}
+DEV void walk_unpack(volatile LC_LDS uint32_t *rec, WalkPos &v, bool lr) {      // the inverse of walk_pack
+  uint32_t w[10]; for (int q = 0; q < 10; ++q) w[q] = rec[q];
+  for (int q = 0; q < 2; ++q) { v.cn4[q] = (uint16_t)(w[0] >> 16 * q); v.cn4[2 + q] = (uint16_t)(w[1] >> 16 * q); v.ct4[q] = (uint16_t)(w[2] >> 16 * q); v.ct4[2 + q] = (uint16_t)(w[3] >> 16 * q); }
+  for (int q = 0; q < 2; ++q) { v.rn2[q] = (uint16_t)(w[4] >> 16 * q); v.rt2[q] = (uint16_t)(w[5] >> 16 * q); }
+  v.col = (int)w[6]; v.P = (int)w[7]; v.pos_in_ref = w[8];
+  v.tumor = (w[9] & 1u) != 0; v.no_spanner = (w[9] & 2u) != 0; v.p_outside = (w[9] & 4u) != 0; v.code = (char)(w[9] >> 8);
+  hp_zero(v.ha); hp_zero(v.hr);                                  // (the minqv fields of the reference stay 0)
+  if (lr) {
+    uint16_t h[18];
+    for (int q = 0; q < 9; ++q) { const uint32_t x = rec[10 + q]; h[2 * q] = (uint16_t)x; h[2 * q + 1] = (uint16_t)(x >> 16); }
+    for (int j = 0; j < 3; ++j) { v.ha.nh[j] = h[j]; v.ha.nq[j] = h[3 + j]; v.ha.th[j] = h[6 + j]; v.ha.tq[j] = h[9 + j]; v.hr.nh[j] = h[12 + j]; v.hr.th[j] = h[15 + j]; }
+  }
+}
+// one lane, one position: the node that spans pathpos, the values at P / refpos, into the lane's LDS record
+DEV void walk_gather(Ctx &c, volatile LC_LDS uint32_t *rec, WalkPos &v, int pathpos, int P, uint32_t refpos, int plen, int np, LC_GLOBAL const uint32_t *pend, bool lr) {
   // first node whose end reaches pathpos (special nodes carry the running position: never the answer unless nothing else is)
   int lo = 0, hi = np;
   while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)(pend[2 * mid] & 0x7FFFFFFFu) >= pathpos) hi = mid; else lo = mid + 1; }
   while (lo < np && (pend[2 * lo] & 0x80000000u)) ++lo;
-  if (lo >= np) fl |= 2u; else if (pend[2 * lo + 1] & 1u) fl |= 1u;
-  uint16_t cn4[4] = {0, 0, 0, 0}, ct4[4] = {0, 0, 0, 0}, rn2[2], rt2[2];
-  if (P < 0 || P >= plen) fl |= 4u; else path_cov_at(c, P, cn4, ct4);
-  ref_cov_at(c, refpos, rn2, rt2);
-  rec[0] = (uint32_t)cn4[0] | ((uint32_t)cn4[1] << 16); rec[1] = (uint32_t)cn4[2] | ((uint32_t)cn4[3] << 16);
-  rec[2] = (uint32_t)ct4[0] | ((uint32_t)ct4[1] << 16); rec[3] = (uint32_t)ct4[2] | ((uint32_t)ct4[3] << 16);
-  rec[4] = (uint32_t)rn2[0] | ((uint32_t)rn2[1] << 16); rec[5] = (uint32_t)rt2[0] | ((uint32_t)rt2[1] << 16);
-  rec[6] = w6; rec[7] = (uint32_t)P; rec[8] = w8; rec[9] = fl | (code << 8);
-  if (lr) {
-    HPc ha, hr;
-    for (int j = 0; j < 3; ++j) { ha.nh[j] = ha.th[j] = ha.nq[j] = ha.tq[j] = 0; }
-    if (!(P < 0 || P >= plen)) path_hp_at(c, P, ha);
-    ref_hp_at(c, refpos, hr);
-    rec[10] = (uint32_t)ha.nh[0] | ((uint32_t)ha.nh[1] << 16); rec[11] = (uint32_t)ha.nh[2] | ((uint32_t)ha.nq[0] << 16); rec[12] = (uint32_t)ha.nq[1] | ((uint32_t)ha.nq[2] << 16);
-    rec[13] = (uint32_t)ha.th[0] | ((uint32_t)ha.th[1] << 16); rec[14] = (uint32_t)ha.th[2] | ((uint32_t)ha.tq[0] << 16); rec[15] = (uint32_t)ha.tq[1] | ((uint32_t)ha.tq[2] << 16);
-    rec[16] = (uint32_t)hr.nh[0] | ((uint32_t)hr.nh[1] << 16); rec[17] = (uint32_t)hr.nh[2] | ((uint32_t)hr.th[0] << 16); rec[18] = (uint32_t)hr.th[1] | ((uint32_t)hr.th[2] << 16);
-  }
-  (void)W;
-}
-DEV void walk_unpack_hp(volatile LC_LDS uint32_t *rc, HPc &ha, HPc &hr) {
-  ha.nh[0] = (uint16_t)rc[10]; ha.nh[1] = (uint16_t)(rc[10] >> 16); ha.nh[2] = (uint16_t)rc[11]; ha.nq[0] = (uint16_t)(rc[11] >> 16); ha.nq[1] = (uint16_t)rc[12]; ha.nq[2] = (uint16_t)(rc[12] >> 16);
-  ha.th[0] = (uint16_t)rc[13]; ha.th[1] = (uint16_t)(rc[13] >> 16); ha.th[2] = (uint16_t)rc[14]; ha.tq[0] = (uint16_t)(rc[14] >> 16); ha.tq[1] = (uint16_t)rc[15]; ha.tq[2] = (uint16_t)(rc[15] >> 16);
-  hr.nh[0] = (uint16_t)rc[16]; hr.nh[1] = (uint16_t)(rc[16] >> 16); hr.nh[2] = (uint16_t)rc[17]; hr.th[0] = (uint16_t)(rc[17] >> 16); hr.th[1] = (uint16_t)rc[18]; hr.th[2] = (uint16_t)(rc[18] >> 16);
-  for (int j = 0; j < 3; ++j) { hr.nq[j] = hr.tq[j] = 0; }
+  v.no_spanner = lo >= np; v.tumor = !v.no_spanner && (pend[2 * lo + 1] & 1u) != 0;
+  walk_pos_load(c, v, P, refpos, plen, lr);
+  walk_pack(rec, v, lr);
 }
 DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
@@ -4992,13 +5027,12 @@ DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
   LC_GLOBAL const uint8_t *ra = W.aln, *pa = W.aln + cap;
   const int refstart = LC_CTX(c).B->ref_start[S.w];
   const int trim5 = wg_uniform(S.trim5);
-  // the transcripts of the path in LDS (the staging area of the build phases); a path with more of them than fit there takes the one-lane form
+  // the transcripts of the path in LDS (the staging area of the build phases); a path with more of them than fit there takes the one-lane driver
 #ifndef LANCET_WAVE_EMU
   LC_LDS TS *ts = (LC_LDS TS *)&lc_shared.lbytes[0];
 #else
   TS *ts = (TS *)(void *)&S.lbytes[0];
 #endif
-  constexpr int LC_TS_LDS = (int)(sizeof(S.lbytes) / sizeof(TS));
   volatile LC_LDS uint32_t *recs = (volatile LC_LDS uint32_t *)&S.acc[0][0];
   static_assert(sizeof(S.acc) >= 64 * 10 * sizeof(uint32_t) && sizeof(S.acc) >= 32 * 19 * sizeof(uint32_t), "64 column records of 10 words, or 32 of 19 (--linked-reads: + the haplotype counts)");
   const bool LR = wg_uniform(S.LR) != 0;
@@ -5024,7 +5058,7 @@ DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
     pend[2 * i] = sp ? ((pstep[i] + (uint32_t)(K - 1)) | 0x80000000u) : (pstep[i] + (uint32_t)n_len(c, nd));
     pend[2 * i + 1] = (!sp && status_cnt_T(c, nd)) ? 1u : 0u;
   }
-  WG_LANE0 { S.wk_stop = 0; S.wk_nts = 0; S.wk_last = -2; S.wk_code = '?'; }
+  WG_LANE0 { S.wk_stop = 0; S.wk_st.nts = 0; S.wk_st.last_col = -2; S.wk_st.code = '?'; }
   WG_SYNC();
   const int ncols = wg_bcast(&S.wk_n);
   // ---- the non-match columns
@@ -5033,68 +5067,37 @@ DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
     WG_FOR(l, LANCET_WG) {
       const int ci = c0 + l;
       if (l < CW && ci < ncols) {
-        const int i = (int)cols[ci];
-        const uint8_t r = ra[i], p = pa[i];
-        const uint32_t code = r == '-' ? (uint32_t)'^' : (p == '-' ? (uint32_t)'v' : (uint32_t)'x');
-        const uint32_t pos_in_ref = E1[i];
-        const int pathpos = (int)(E2[i] + (p != '-' ? 1u : 0u));
-        walk_gather(c, recs + RS * l, pathpos, pathpos - 1, pos_in_ref + (uint32_t)trim5, plen, np, pend, (uint32_t)i, pos_in_ref, code, LR);
+        WalkPos v;
+        v.col = (int)cols[ci];
+        const uint8_t r = ra[v.col], p = pa[v.col];
+        v.code = column_code(r, p); v.pos_in_ref = E1[v.col];
+        const int pathpos = (int)(E2[v.col] + (p != '-' ? 1u : 0u));
+        walk_gather(c, recs + RS * l, v, pathpos, pathpos - 1, v.pos_in_ref + (uint32_t)trim5, plen, np, pend, LR);
       }
     }
     WG_SYNC();
     WG_LANE0 {
       const int cnt = ncols - c0 < CW ? ncols - c0 : CW;
-      int nts = S.wk_nts, last_col = S.wk_last; char code = (char)S.wk_code, prev_code;
-      for (int l = 0; l < cnt && !S.wk_stop; ++l) {
-        volatile LC_LDS uint32_t *rc = recs + RS * l;
-        const int i = (int)rc[6], P = (int)rc[7]; const uint32_t pos_in_ref = rc[8], fl = rc[9] & 0xFFu;
-        prev_code = (last_col == i - 1) ? code : '=';
-        last_col = i; code = (char)(rc[9] >> 8);
-        if (fl & 2u) { S.wk_stop = 1; break; }                           // no node spans the position: the reference's loop ends here
-        if (fl & 4u) { OVF(c); S.wk_stop = 2; break; }                   // the reference reads coverageN[-1] here (undefined)
-        const bool within_tumor = (fl & 1u) != 0;
-        uint16_t cn4[4] = {(uint16_t)rc[0], (uint16_t)(rc[0] >> 16), (uint16_t)rc[1], (uint16_t)(rc[1] >> 16)};
-        uint16_t ct4[4] = {(uint16_t)rc[2], (uint16_t)(rc[2] >> 16), (uint16_t)rc[3], (uint16_t)(rc[3] >> 16)};
-        uint16_t rn2[2] = {(uint16_t)rc[4], (uint16_t)(rc[4] >> 16)}, rt2[2] = {(uint16_t)rc[5], (uint16_t)(rc[5] >> 16)};
-        const unsigned rrpos = pos_in_ref + (unsigned)refstart + (unsigned)trim5;
-        HPc ha, hr;
-        if (LR) walk_unpack_hp(rc, ha, hr); else { for (int j = 0; j < 3; ++j) { ha.nh[j] = ha.th[j] = ha.nq[j] = ha.tq[j] = 0; hr.nh[j] = hr.th[j] = hr.nq[j] = hr.tq[j] = 0; } }
-        if (nts > 0 && prev_code != '=') {
-          auto &t = ts[nts - 1];
-          if (within_tumor) t.somatic = true;
-          const int reflen_before = t.col1 - t.col0 + 1;
-          t.col1 = i; t.end_pos = (uint32_t)P; t.ref_end_pos = pos_in_ref;
-          if (code == '^' && t.code == code && t.pos == rrpos) { ts_add_alt(t, cn4, ct4); if (LR) ts_hp_add_alt(t, ha); }
-          else if (code == 'v' && t.code == code && (t.pos + (unsigned)(reflen_before + 1)) == rrpos) { ts_add_ref(t, rn2, rt2); if (LR) ts_hp_add_ref(t, hr); }
-          else if (code == 'x' || t.code != code) { t.code = 'c'; ts_add_alt(t, cn4, ct4); ts_add_ref(t, rn2, rt2); if (LR) { ts_hp_add_alt(t, ha); ts_hp_add_ref(t, hr); } }
-        } else {
-          int pr = i - 1, pq = i - 1;
-          while (pr >= 0 && ra[pr] != 'A' && ra[pr] != 'C' && ra[pr] != 'G' && ra[pr] != 'T') --pr;
-          while (pq >= 0 && pa[pq] != 'A' && pa[pq] != 'C' && pa[pq] != 'G' && pa[pq] != 'T') --pq;
-          if (pr < 0 || pq < 0) { OVF(c); S.wk_stop = 2; break; }        // reference: assert(pr >= 0)
-          if (nts >= LC_MAXTS) { OVF(c); S.wk_stop = 2; break; }
-          if (nts >= LC_TS_LDS) { S.wk_stop = 3; break; }                 // more transcripts than LDS holds: the one-lane form, from the start
-          auto &t = ts[nts++];
-          t.pos = rrpos; t.ref_pos = pos_in_ref; t.start_pos = (uint32_t)(P + 1); t.code = code; t.end_pos = (uint32_t)P; t.ref_end_pos = pos_in_ref;
-          t.col0 = i; t.col1 = i; t.somatic = within_tumor; t.prev_bp_ref = (char)ra[pr]; t.prev_bp_alt = (char)pa[pq];
-          for (int q = 0; q < 4; ++q) { acc_init(t.aN[q], cn4[q]); acc_init(t.aT[q], ct4[q]); }
-          for (int q = 0; q < 2; ++q) { acc_init(t.rN[q], rn2[q]); acc_init(t.rT[q], rt2[q]); }
-          ts_hp_init(t, ha, hr);                                          // (zeros without --linked-reads)
-        }
+      WalkState st = walk_state_load(S);
+      int stop = WALK_GO;
+      for (int l = 0; l < cnt && stop == WALK_GO; ++l) {
+        WalkPos v;
+        walk_unpack(recs + RS * l, v, LR);
+        stop = walk_column(c, ts, st, LC_TS_LDS, v, ra, pa, v.pos_in_ref + (unsigned)refstart + (unsigned)trim5, LR);
       }
-      S.wk_nts = nts; S.wk_last = last_col; S.wk_code = (int)code;
+      walk_state_store(S, st); S.wk_stop = stop;
     }
     if (wg_bcast(&S.wk_stop)) break;
   }
-  if (wg_bcast(&S.wk_stop) == 2) return;                                  // work-space limit / undefined read: the window is given up
-  if (wg_bcast(&S.wk_stop) == 3) { WG_LANE0 { process_path_walk(c, np, plen, L, complete); } return; }
+  if (wg_bcast(&S.wk_stop) == WALK_OVF) return;                           // work-space limit / undefined read: the window is given up
+  if (wg_bcast(&S.wk_stop) == WALK_FULL) { WG_LANE0 { process_path_walk(c, np, plen, L, complete); } return; }   // the one-lane driver, from the start
   WG_LANE0 { evt(c, EV_PATH, (uint32_t)complete, (uint32_t)S.tmp3, (uint32_t)S.wk[0], (uint32_t)S.wk[1], (uint32_t)S.wk[2], (uint32_t)S.wk[3]); }
   // ---- the transcripts: K + 1 positions past the end of every indel / complex one, then the record
-  const int nts = wg_bcast(&S.wk_nts);
+  const int nts = wg_bcast(&S.wk_st.nts);
   SUBPHASE(c, 4, 5);
   for (int ti = 0; ti < nts; ++ti) {
-    WG_LANE0 { const auto &t = ts[ti]; S.wk_code = (int)t.code; S.wk_tend = (int)t.end_pos; S.wk_tref = (int)t.ref_end_pos; S.wk_stop = 0; }
-    if ((char)wg_bcast(&S.wk_code) != 'x') {
+    WG_LANE0 { const auto &t = ts[ti]; S.wk_st.code = (int)t.code; S.wk_tend = (int)t.end_pos; S.wk_tref = (int)t.ref_end_pos; S.wk_stop = 0; }
+    if ((char)wg_bcast(&S.wk_st.code) != 'x') {
       const int tend = wg_bcast(&S.wk_tend), tref = wg_bcast(&S.wk_tref);
       for (int j0 = 0; j0 <= K; j0 += CW) {
         WG_FOR(l, LANCET_WG) {
@@ -5103,28 +5106,17 @@ DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
             const unsigned idx1 = (unsigned)tend + (unsigned)j;
             // (idx1 >= plen: the path contributes nothing at this position, the reference still does)
             // contig_at(idx1) and coverage[idx1]: the node search is made for idx1 itself here (not idx1 + 1 as in the column walk)
-            walk_gather(c, recs + RS * l, (int)idx1, idx1 < (unsigned)plen ? (int)idx1 : -1, (uint32_t)tref + (uint32_t)trim5 + (uint32_t)j, plen, np, pend, (uint32_t)j, idx1 < (unsigned)plen ? 1u : 0u, 0u, LR);
+            WalkPos v; v.col = j; v.code = 0; v.pos_in_ref = 0;
+            walk_gather(c, recs + RS * l, v, (int)idx1, idx1 < (unsigned)plen ? (int)idx1 : -1, (uint32_t)tref + (uint32_t)trim5 + (uint32_t)j, plen, np, pend, LR);
           }
         }
         WG_SYNC();
         WG_LANE0 {
-          auto &t = ts[ti];
           const int cnt = K + 1 - j0 < CW ? K + 1 - j0 : CW;
           for (int l = 0; l < cnt; ++l) {
-            volatile LC_LDS uint32_t *rc = recs + RS * l;
-            HPc ha, hr;
-            if (LR) walk_unpack_hp(rc, ha, hr);
-            if (rc[8]) {                                                   // idx1 < plen
-              if (rc[9] & 2u) { S.wk_stop = 1; break; }                    // contig_at == NIL: the reference leaves the loop over j
-              if (rc[9] & 1u) t.somatic = true;
-              uint16_t cn4[4] = {(uint16_t)rc[0], (uint16_t)(rc[0] >> 16), (uint16_t)rc[1], (uint16_t)(rc[1] >> 16)};
-              uint16_t ct4[4] = {(uint16_t)rc[2], (uint16_t)(rc[2] >> 16), (uint16_t)rc[3], (uint16_t)(rc[3] >> 16)};
-              ts_add_alt(t, cn4, ct4);
-              if (LR) ts_hp_add_alt(t, ha);
-            }
-            uint16_t rn2[2] = {(uint16_t)rc[4], (uint16_t)(rc[4] >> 16)}, rt2[2] = {(uint16_t)rc[5], (uint16_t)(rc[5] >> 16)};
-            ts_add_ref(t, rn2, rt2);
-            if (LR) ts_hp_add_ref(t, hr);
+            WalkPos v;
+            walk_unpack(recs + RS * l, v, LR);
+            if (!walk_extend(ts[ti], v, LR)) { S.wk_stop = 1; break; }
           }
         }
         if (wg_bcast(&S.wk_stop)) break;
@@ -5140,50 +5132,13 @@ DEVNI void process_path_walk_wg(Ctx &c, int np, int plen, int L, int complete) {
     static_assert(sizeof(S.acc) >= 2048, "path string staged for findTandems");
     WG_FOR(i, stg_hi - stg_lo) { stg[i] = W.pseq[stg_lo + i]; }
     WG_SYNC();
-    WG_LANE0 {
-      auto &t = ts[ti];
-      const bool x = t.code == 'x';
-      uint16_t RCNF = t.rN[0].mn, RCNR = t.rN[1].mn, RCTF = t.rT[0].mn, RCTR = t.rT[1].mn;
-      uint16_t ACNF = x ? t.aN[2].mn : t.aN[0].mn, ACNR = x ? t.aN[3].mn : t.aN[1].mn;
-      if (!x) { ACNF = t.aN[0].mnz; ACNR = t.aN[1].mnz; }     // getMinNon0Cov*: code != 'x' -> .fwd/.rev
-      uint16_t ACTF = x ? t.aT[2].mn : t.aT[0].mn, ACTR = x ? t.aT[3].mn : t.aT[1].mn;
-      if (t.somatic) { RCNF = acc_mean(t.rN[0]); RCNR = acc_mean(t.rN[1]); RCTF = acc_mean(t.rT[0]); RCTR = acc_mean(t.rT[1]); ACNF = 0; ACNR = 0; }
-      uint16_t cov[8] = {RCNF, RCNR, RCTF, RCTR, ACNF, ACNR, ACTF, ACTR};
-      uint16_t hp12[12]; for (int q = 0; q < 12; ++q) hp12[q] = 0;       // HPRN HPRT HPAN HPAT as {hp1, hp2, hp0} (Graph.cc:1091-1128, 1166-1169; process_path_walk has the same lines)
-      if (LR) {
-        const uint32_t nref = t.rN[0].n;
-        auto mean = [&](uint16_t sum) -> uint16_t { return nref > 0 ? (uint16_t)((float)sum / (float)nref) : (uint16_t)0; };
-        uint16_t RN[3], RT[3], AN[3], AT[3];
-        for (int j = 0; j < 3; ++j) {
-          RN[j] = t.hrmnN[j]; RT[j] = t.hrmnT[j];
-          AN[j] = x ? t.haqN[j] : t.hamnN[j]; AT[j] = x ? t.haqT[j] : t.hamnT[j];
-          if (t.somatic) { RT[j] = mean(t.hrsumT[j]); RN[j] = mean(t.hrsumN[j]); AN[j] = 0; }
-        }
-        const uint16_t v[12] = {RN[1], RN[2], RN[0], RT[1], RT[2], RT[0], AN[1], AN[2], AN[0], AT[1], AT[2], AT[0]};
-        for (int q = 0; q < 12; ++q) hp12[q] = v[q];
-      }
-      if (LC_CTX(c).C->evt_cap) {
-        evt(c, EV_TS, t.pos, (uint32_t)(t.col1 - t.col0 + 1), ((uint32_t)RCNF << 16) | RCNR, ((uint32_t)RCTF << 16) | RCTR,
-            ((uint32_t)ACNF << 16) | ACNR, ((uint32_t)ACTF << 16) | ACTR, ((uint32_t)(uint8_t)t.prev_bp_ref << 8) | (uint8_t)t.prev_bp_alt);
-        evt_bytes(c, ra + t.col0, (uint32_t)(t.col1 - t.col0 + 1));
-        evt_bytes(c, pa + t.col0, (uint32_t)(t.col1 - t.col0 + 1));
-        evt_bytes(c, (const uint8_t *)hp12, 24);
-      }
-      if (ACNF > 0 || ACNR > 0 || ACTF > 0 || ACTR > 0) {
-        int LEN = 0, ml = 0; uint8_t motif[64];
-        bool ans = find_tandems_local(c, W.pseq, plen, (int)t.start_pos, &LEN, motif, &ml, stg, stg_lo, stg_hi);
-        TS tc; tc.pos = t.pos; tc.ref_pos = t.ref_pos; tc.start_pos = t.start_pos; tc.end_pos = t.end_pos; tc.ref_end_pos = t.ref_end_pos; tc.col0 = t.col0; tc.col1 = t.col1;
-        tc.code = t.code; tc.prev_bp_ref = t.prev_bp_ref; tc.prev_bp_alt = t.prev_bp_alt; tc.somatic = t.somatic;      // (what emit_variant reads; short reads: no haplotype fields)
-        emit_variant(c, tc, cov, LEN, motif, ml, ans, ra, pa, hp12, plen);
-      }
-    }
+    WG_LANE0 { walk_record(c, ts[ti], ra, pa, plen, LR, stg, stg_lo, stg_hi); }
     SUBPHASE(c, 4, 5);
   }
   SUBPHASE(c, 4, 7);
   WG_LANE0 { evt(c, EV_PATH_END); }
   WG_FOR(i, np) { dev_atomic_add(&W.gr[W.pnodes[i]].onref, 1u); }
-  // counters of eka (perfect / withsnps / withindel / withmix) ride in tmp0..tmp2 + part[0]
-  WG_LANE0 { const int snp_bp = S.wk[1], ins_bp = S.wk[2], del_bp = S.wk[3]; if ((snp_bp + ins_bp + del_bp) == 0) ++S.tmp0; else if (snp_bp == 0) ++S.tmp1; else if ((ins_bp + del_bp) == 0) ++S.tmp2; else ++S.part[0]; }
+  WG_LANE0 { eka_count(S); }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -5332,11 +5287,9 @@ DEVNI void count_ref_path(Ctx &c) {
         }
       }
       if (wg_bcastu(&S.part[3]) != 0) break;
-      // the one-lane walk with everything walk_prepare makes, on every path (the emulator's comparison form; tuning builds: --linked-reads windows)
+      // the one-lane walk with everything walk_prepare makes, on every path (the emulator's comparison form)
 #ifdef LANCET_WAVE_EMU
       const bool old_walk = getenv("LANCET_OLD_WALK") != nullptr;
-#elif defined(LANCET_LR_WALK_LANE0)
-      const bool old_walk = wg_uniform(S.LR) != 0;
 #else
       const bool old_walk = false;
 #endif

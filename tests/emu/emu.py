@@ -40,6 +40,11 @@ def lib():
     return _LIB
 
 
+def ts_lds_cap() -> int:
+    """Transcripts of one path the window kernel's LDS staging area holds (kernels.h LC_TS_LDS) in the library FAT selects."""
+    return int(lib().lancet_emu_ts_lds_cap())
+
+
 LAST_EVENTS = []
 LAST_BIGLIST = [0]           # windows handed to the 1024-lane configuration of the LDS build kernel, last run
 LAST_AHEAD = [0, 0]          # graphs built ahead at a later k / taken by the window kernel, last run

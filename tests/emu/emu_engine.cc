@@ -140,6 +140,7 @@ extern "C" uint32_t lancet_emu_n_svc_posted(void *h) { return ((EmuResult *)h)->
 extern "C" uint32_t lancet_emu_n_svc_built(void *h) { return ((EmuResult *)h)->n_svc_built; }
 extern "C" uint32_t lancet_emu_n_svc_stolen(void *h) { return ((EmuResult *)h)->n_svc_stolen; }
 extern "C" void lancet_emu_free(void *h) { delete (EmuResult *)h; }
+extern "C" int lancet_emu_ts_lds_cap() { return LC_TS_LDS; }      // transcripts of one path the LDS staging area holds (tests/walk_cases.py many_ts, ts_exact)
 
 // repeat_scan both ways (bit-parallel LDS version vs the byte-wise restatement) for the unit test
 extern "C" void lancet_emu_repeat_scan(const uint8_t *s, int len, int mm, int bitparallel, int *outE, int *outM) {

@@ -31,17 +31,24 @@ def _engine_equals_oracle(batch, p, trace):
 
 
 def test_walk_cases_as_one_batch():
+    """The short-read cases, one small batch per (k, read length): one engine means one set of parameters."""
     names = [c for c in wc.CASES if not c.endswith("_lr")]
-    batch = workload.concat_batches([wc.make(c)[0] for c in names])
-    ov, otr = _engine_equals_oracle(batch, wc.params(names[0]), trace=True)
-    assert wc.paths_of(otr) == [p for c in names for p in wc.PATHS[c]]               # every case still reaches its route
-    assert len(ov) == sum(wc.N_RECORDS[c] for c in names)
+    groups = {}
+    for c in names:
+        groups.setdefault(wc.read_len_k(c), []).append(c)
+    assert sorted(c for g in groups.values() for c in g) == sorted(names) and len(groups) > 1
+    for group in groups.values():
+        batch = workload.concat_batches([wc.make(c)[0] for c in group])
+        ov, otr = _engine_equals_oracle(batch, wc.params(group[0]), trace=True)
+        assert wc.paths_of(otr) == [p for c in group for p in wc.PATHS[c]]           # every case still reaches its route
+        assert len(ov) == sum(wc.N_RECORDS[c] for c in group)
 
 
-def test_walk_case_with_linked_reads():
-    batch, p = wc.make("snv1_lr")
+@pytest.mark.parametrize("case", [c for c in wc.CASES if c.endswith("_lr")])
+def test_walk_case_with_linked_reads(case):
+    batch, p = wc.make(case)
     ov, otr = _engine_equals_oracle(batch, p, trace=True)
-    assert wc.paths_of(otr) == wc.PATHS["snv1_lr"] and len(ov) == 1
+    assert wc.paths_of(otr) == wc.PATHS[case] and len(ov) == wc.N_RECORDS[case]
 
 
 def test_scan_batch_of_256_windows():
