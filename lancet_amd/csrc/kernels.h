@@ -4421,10 +4421,17 @@ DEVNI bool align_fill_band(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL
 }
 
 // traceback into W.aln: returns alignment length; ref_aln at aln[0..L), path_aln at aln[cap..cap+L) (ASCII)
-// Lane 0 follows the traceback bytes and only NOTES every column (i << 16 | j << 2 | kind: 0 both characters, 1 reference character
+// The walk follows the traceback bytes and only NOTES every column (i << 16 | j << 2 | kind: 0 both characters, 1 reference character
 // against '-', 2 '-' against path character) in W.scratch; align_traceback_fill (all lanes) writes the two aligned strings from the
-// notes -- the walk itself then has no loads but the traceback bytes, eight cells of a diagonal at a time.
-DEVNI int align_traceback(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL const uint8_t *Tx, int m) {
+// notes -- the walk itself then has no loads but the traceback bytes.
+// Two forms of the same walk:
+//   align_traceback_runs   the walk by runs, on the device (wave 0) and in the emulator: 64 bytes are fetched along the line the walk is
+//                          on (the diagonal; the column / the row while a gap is extended) and one trip consumes the whole run of cells
+//                          that stay on that line -- its notes are one store -- up to the cell that ends it, which takes the one-cell rules;
+//   align_traceback_cells  one cell per trip by one lane, eight cells of a diagonal fetched at a time: the emulator's comparison form
+//                          (LANCET_OLD_TRACEBACK), as LANCET_OLD_WALK is for the transcript walk.
+#ifdef LANCET_WAVE_EMU
+DEVNI int align_traceback_cells(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL const uint8_t *Tx, int m) {
   LC_GLOBAL Work &W = *LC_CTX(c).W;
   const int cap = (int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2;
   LC_GLOBAL uint32_t *cols = W.scratch;
@@ -4465,68 +4472,113 @@ DEVNI int align_traceback(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL 
   }
   return L;
 }
-// The same walk by the whole wave (all lanes: returns the length, uniform).  Host emulation: the one-lane walk above.
-// GPU: every lane follows the walk redundantly (the state is wave-uniform); the traceback bytes are fetched 64 at a time, one per
-// lane, along the line the walk is on -- the diagonal, or the column / row while a gap is being extended -- and handed around with a
-// wave shuffle, so the walk pays one memory round trip per 64 cells (or per turn) instead of one per 8; the notes are kept one per
-// lane and stored 64 at a time.
+#endif
+// the traceback byte of cell (ii, jj) as the walk reads it: 0 outside the matrix and outside the band
+DEV uint32_t align_tb_byte(LC_GLOBAL const uint8_t *tbp, int band, int blo, int n, int ii, int jj) {
+  if (ii < 0 || jj < 0) return 0u;
+  if (!band) return tbp[LC_TB(ii, jj, n)];
+  if (ii == 0) return (uint32_t)((jj == 0 ? 3 : 2) | (0 << 2) | (2 << 4));          // the borders are not stored in the band layout
+  if (jj == 0) return (uint32_t)(1 | (2 << 2) | (0 << 4));
+  const int tt = ii + jj, oo = jj - ii, li = (oo - blo - ((tt - blo) & 1)) >> 1;
+  return (li >= 0 && li < 64) ? tbp[(size_t)tt * 64 + (size_t)li] : 0u;
+}
+// The 64 cells of a fetch.  The two builds differ here and nowhere else in the walk: on the device a cell per lane of the wave, the
+// mask of the cells that end a run is a wave ballot; in the emulator an array and a loop stand in for the lanes.
+#ifndef LANCET_WAVE_EMU
+struct TbLine {
+  uint32_t v;
+  template <class F> DEVM void fetch(F cell) { v = cell((int)threadIdx.x); }
+  template <class P> DEVM unsigned long long stops(P stop) const { return __ballot(stop((int)threadIdx.x, v) ? 1 : 0); }
+  DEVM uint32_t at(int q) const { return (uint32_t)__builtin_amdgcn_readlane((int)v, lc_sgpr(q)); }
+};
+#define TB_EACH_LANE(l) for (int l = (int)threadIdx.x, l##_once = 1; l##_once; l##_once = 0)
+#else
+struct TbLine {
+  uint32_t v[64];
+  template <class F> DEVM void fetch(F cell) { for (int l = 0; l < 64; ++l) v[l] = cell(l); }
+  template <class P> DEVM unsigned long long stops(P stop) const { unsigned long long s = 0; for (int l = 0; l < 64; ++l) { if (stop(l, v[l])) s |= 1ULL << l; } return s; }
+  DEVM uint32_t at(int q) const { return v[q]; }
+};
+#define TB_EACH_LANE(l) for (int l = 0; l < 64; ++l)
+#endif
+// The walk by runs (device: every lane of wave 0, the state is wave-uniform and kept in scalar registers): the length, -1 where the
+// reference would read out of bounds.
+DEV int align_traceback_runs(Ctx &c, int n, int m) {
+  LC_GLOBAL Work &W = *LC_CTX(c).W; LC_WS &S = LC_SREF(c);
+  const int cap = lc_sgpr((int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2);
+  LC_GLOBAL uint32_t *cols = W.scratch;
+  LC_GLOBAL const uint8_t *tbp = W.tb;
+  const int band = lc_sgpr((int)S.al_band), blo = lc_sgpr((int)S.al_lo);
+  n = lc_sgpr(n); m = lc_sgpr(m);
+  int i = n, j = m, L = 0;
+  bool forcex = false, forcey = false;
+  int ci = 0, cj = 0, cdir = -1;
+  unsigned long long stop = 0;
+  TbLine line;
+  while (i > 0 || j > 0) {
+    if (i < 0 || j < 0 || L >= cap) return -1;                            // the reference would read out of bounds here
+    const int want = forcex ? 1 : (forcey ? 2 : 0);
+    int q = -1;                                                         // where the walk stands in the fetched line
+    if (cdir == want) {
+      if (want == 0) { if (ci - i == cj - j) q = ci - i; }
+      else if (want == 1) { if (cj == j) q = ci - i; }
+      else { if (ci == i) q = cj - j; }
+    }
+    if (q < 0 || q > 63) {
+      cdir = want; ci = i; cj = j; q = 0;
+      line.fetch([&](int l) { return align_tb_byte(tbp, band, blo, n, want == 2 ? i : i - l, want == 1 ? j : j - l); });
+      // the cells that do not continue the line: a turn (or the matrix's edge) on the diagonal, the end of the gap (or the border) under a force
+      stop = line.stops([&](int l, uint32_t b) {
+        if (want == 0) return (b & 3u) != 0u || i - l < 0 || j - l < 0;
+        if (want == 1) return ((b >> 2) & 3u) == 0u || (b & 3u) == 3u || i - l < 1;
+        return ((b >> 4) & 3u) == 0u || (b & 1u) != 0u || j - l < 1;             // (a '<' cell goes before a pending row force: t == 1 or 3)
+      });
+    }
+    const unsigned long long rem = stop >> q;
+    int r = rem ? (int)__builtin_ctzll(rem) : 64 - q;
+    if (r > cap - L) r = cap - L;
+    if (r > 0) {                                                        // a run of r cells: their notes in one store
+      const int di = want == 2 ? 0 : 1, dj = want == 1 ? 0 : 1;
+      TB_EACH_LANE(l) { const int x = l - q; if (x >= 0 && x < r) cols[L + x] = ((uint32_t)(i - x * di) << 16) | ((uint32_t)(j - x * dj) << 2) | (uint32_t)want; }
+      i -= r * di; j -= r * dj; L += r;
+      continue;
+    }
+    // the cell that ended the run
+    const uint32_t b = line.at(q);
+    const int t = (int)(b & 3u), x = (int)((b >> 2) & 3u), y = (int)((b >> 4) & 3u);
+    uint32_t v;
+    if (t == 3) break;
+    else if (forcex) { if (i < 1) return -1; v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 1u; if (x == 0) forcex = false; --i; }
+    else if (t == 1) { v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 1u; if (x == 1) forcex = true; --i; }
+    else if (forcey) { if (j < 1) return -1; v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 2u; if (y == 0) forcey = false; --j; }
+    else if (t == 2) { v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 2u; if (y == 1) forcey = true; --j; }
+    else { v = ((uint32_t)i << 16) | ((uint32_t)j << 2); --i; --j; }
+    TB_EACH_LANE(l) { if (l == q) cols[L] = v; }
+    ++L;
+  }
+  return L;
+}
+#ifdef LANCET_WAVE_EMU
+DEVNI int align_traceback(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL const uint8_t *Tx, int m) {
+  if (getenv("LANCET_OLD_TRACEBACK") != nullptr) return align_traceback_cells(c, Sx, n, Tx, m);
+  const int L = align_traceback_runs(c, n, m);
+  if (L < 0) { OVF(c); return 0; }
+  return L;
+}
+#endif
+// all lanes: returns the length (uniform).  The fat form walks on wave 0 only.
 DEVNI int align_traceback_wg(Ctx &c, LC_GLOBAL const uint8_t *Sx, int n, LC_GLOBAL const uint8_t *Tx, int m) {
   LC_WS &S = LC_SREF(c);
 #ifdef LANCET_WAVE_EMU
   WG_LANE0 { S.al_L = align_traceback(c, Sx, n, Tx, m); }
-  return wg_bcast(&S.al_L);
 #else
-  LC_GLOBAL Work &W = *LC_CTX(c).W;
   (void)Sx; (void)Tx;
   if (threadIdx.x < 64) {
-    const int lane = (int)threadIdx.x;
-    const int cap = (int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2;
-    LC_GLOBAL uint32_t *cols = W.scratch;
-    LC_GLOBAL const uint8_t *tbp = W.tb;
-    const int band = S.al_band, blo = S.al_lo;
-    int i = n, j = m, L = 0;
-    bool forcex = false, forcey = false, bad = false;
-    int ci = 0, cj = 0, cdir = -1;
-    uint32_t mine = 0, note = 0;
-    while (i > 0 || j > 0) {
-      if (i < 0 || j < 0 || L >= cap) { bad = true; break; }              // the reference would read out of bounds here
-      const int want = forcex ? 1 : (forcey ? 2 : 0);
-      int q = -1;
-      if (cdir == want) {
-        if (want == 0) { if (ci - i == cj - j) q = ci - i; }
-        else if (want == 1) { if (cj == j) q = ci - i; }
-        else { if (ci == i) q = cj - j; }
-      }
-      if (q < 0 || q > 63) {
-        cdir = want; ci = i; cj = j; q = 0;
-        const int ii = want == 2 ? i : i - lane, jj = want == 1 ? j : j - lane;
-        uint32_t bb = 0;
-        if (ii >= 0 && jj >= 0) {
-          if (!band) bb = tbp[LC_TB(ii, jj, n)];
-          else if (ii == 0) bb = (uint32_t)((jj == 0 ? 3 : 2) | (0 << 2) | (2 << 4));        // the borders are not stored in the band layout
-          else if (jj == 0) bb = (uint32_t)(1 | (2 << 2) | (0 << 4));
-          else { const int tt = ii + jj, oo = jj - ii; const int li = (oo - blo - ((tt - blo) & 1)) >> 1; bb = (li >= 0 && li < 64) ? tbp[(size_t)tt * 64 + (size_t)li] : 0u; }
-        }
-        mine = bb;
-      }
-      const uint32_t b = (uint32_t)__shfl((int)mine, q, 64);
-      const int t = (int)(b & 3u), x = (int)((b >> 2) & 3u), y = (int)((b >> 4) & 3u);
-      uint32_t v;
-      if (t == 3) break;
-      else if (forcex) { if (i < 1) { bad = true; break; } v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 1u; if (x == 0) forcex = false; --i; }
-      else if (t == 1) { v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 1u; if (x == 1) forcex = true; --i; }
-      else if (forcey) { if (j < 1) { bad = true; break; } v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 2u; if (y == 0) forcey = false; --j; }
-      else if (t == 2) { v = ((uint32_t)i << 16) | ((uint32_t)j << 2) | 2u; if (y == 1) forcey = true; --j; }
-      else { v = ((uint32_t)i << 16) | ((uint32_t)j << 2); --i; --j; }
-      if (lane == (L & 63)) note = v;
-      ++L;
-      if ((L & 63) == 0) cols[L - 64 + lane] = note;
-    }
-    if (!bad && lane < (L & 63)) cols[(L & ~63) + lane] = note;
-    if (lane == 0) { if (bad) { OVF(c); L = 0; } S.al_L = L; }
+    int L = align_traceback_runs(c, n, m);
+    if (threadIdx.x == 0) { if (L < 0) { OVF(c); L = 0; } S.al_L = L; }
   }
-  return wg_bcast(&S.al_L);
 #endif
+  return wg_bcast(&S.al_L);
 }
 // A note keeps j in 14 bits (and i in 16): the longest path string the notes can hold.  lancet_engine_create refuses parameters whose
 // path_cap is above it, the test hooks refuse such a string.
