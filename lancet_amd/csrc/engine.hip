@@ -550,8 +550,7 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
     node_cap1 = mean_bases / 4 <= 8192 ? 8192u : 16384u;
   }
   e->caps = lc_caps_for_batch(b, &e->params, e->evt_cap, node_cap1, 1);
-  uint32_t nodes2 = e->max_nodes_limit;
-  if (!e->max_nodes_env) for (int w = 0; w < nw; ++w) if (b->read_begin[w + 1] - b->read_begin[w] >= 0xFFFFu) { nodes2 = std::max(nodes2, 1u << 20); break; }
+  const uint32_t nodes2 = lc_tier2_nodes_for_batch(b, e->max_nodes_limit, !e->max_nodes_env);
   e->caps2 = lc_caps_for_batch(b, &e->params, e->evt_cap, nodes2, 2);
   e->caps2.wide_ids = e->no_fat ? 0u : 1u;                     // (LANCET_NO_FAT: the one-wave kernel re-runs, with its 16-bit limit)
   e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;

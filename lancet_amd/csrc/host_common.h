@@ -50,6 +50,11 @@ static inline PreLayout lc_pre_layout_for_batch(const lancet_window_batch *b, si
   return (deep && n_areas * (size_t)wide.stride <= budget) ? wide : narrow;
 }
 
+// Node limit of the re-run tier: `limit` (65 536 unless LANCET_MAX_NODES says otherwise), 2^20 when `grow` and a window has 65 535 reads or more.
+static inline uint32_t lc_tier2_nodes_for_batch(const lancet_window_batch *b, uint32_t limit, bool grow) {
+  if (grow) for (int w = 0; w < b->n_windows; ++w) if (b->read_begin[w + 1] - b->read_begin[w] >= 0xFFFFu) return limit > (1u << 20) ? limit : (1u << 20);
+  return limit;
+}
 // Work-space caps for a batch: the largest window decides.
 // tier 1 = the common case (small tables: cheap to clear, cache/TLB friendly); tier 2 = worst case for the window
 // shapes in the batch, used to re-run the windows that overflowed tier 1.
@@ -80,6 +85,10 @@ static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const l
   if (nodes > max_nodes_limit) nodes = max_nodes_limit;
   c.node_cap = nodes;
   c.table_cap = lc_pow2_ge(2 * nodes);
+  // The flagged occurrences of the mate-overlap replay share todo[] with the slot -> node table.  Tier 1 keeps that size (its windows re-run
+  // when the list fills up); the re-run tier holds one entry per occurrence: a short-insert library at a few hundred x flags more
+  // occurrences than a 65 536-node window has slots (8 windows of ~3 200 overlapping 150-base reads: 165 k of 400 k).
+  c.todo_cap = tier == 1 || c.occ_cap < c.table_cap ? c.table_cap : c.occ_cap;
   c.bucket_cap = lc_bucket_cap_for(nodes);
   c.special_cap = tier == 1 ? 64u : 4096u;     /* source + sink per component that touches the reference, per build */
   uint32_t maxk = (uint32_t)(p->max_k > 0 ? p->max_k : 101);
@@ -135,7 +144,7 @@ static inline size_t lc_work_carve(Work *w, char *base, const EngineCaps &c) {
   t.chunk = k.take<uint32_t>(2 * (((size_t)c.reads_cap + MW / LC_SEG + 2) / 64 + 2));
   t.occ = k.take<uint32_t>(c.occ_cap);
   t.slots = k.take<uint32_t>(4 * (size_t)c.table_cap);
-  t.todo = k.take<uint32_t>(c.table_cap);
+  t.todo = k.take<uint32_t>(c.todo_cap > c.table_cap ? c.todo_cap : c.table_cap);
   t.mv = k.take<uint32_t>((c.wide_ids ? 8 : 4) * (size_t)c.occ_cap);
   t.slot_key = k.take<unsigned long long>((size_t)c.table_cap * LC_NWMAX);
   t.bitmap = k.take<uint32_t>((c.occ_cap + c.special_cap) / 32 + 4);   /* also the visited set of the component search (node ids) */

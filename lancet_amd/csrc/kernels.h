@@ -1771,7 +1771,7 @@ DEVNI void build_csr(Ctx &c) {
           if (hit) {
             W.occ[o0 + p] = oc | 0x40000000u;
             uint32_t t = dev_atomic_add((LC_LDS uint32_t *)&S.tmp1, 1u);
-            if (t < LC_CTX(c).C->table_cap) W.todo[t] = (r << 10) | (uint32_t)p; else OVF(c);
+            if (t < C.todo_cap) W.todo[t] = (r << 10) | (uint32_t)p; else OVF(c);
           }
         }
       }
@@ -1819,7 +1819,7 @@ DEVNI void build_csr(Ctx &c) {
         if (hit) {
           W.occ[o0 + p] = oc | 0x40000000u;
           uint32_t t = dev_atomic_add((LC_LDS uint32_t *)&S.tmp1, 1u);
-          if (t < LC_CTX(c).C->table_cap) W.todo[t] = ((uint32_t)r << 10) | (uint32_t)p; else OVF(c);
+          if (t < C.todo_cap) W.todo[t] = ((uint32_t)r << 10) | (uint32_t)p; else OVF(c);
         }
       }
       WG_SYNC();
@@ -1863,7 +1863,7 @@ DEVNI void build_csr(Ctx &c) {
   //      reference's lower_bound over the names of that prefix.
   {
     const uint32_t ntodo0 = (uint32_t)wg_bcast(&S.tmp1);
-    const uint32_t ntodo = ntodo0 > LC_CTX(c).C->table_cap ? LC_CTX(c).C->table_cap : ntodo0;
+    const uint32_t ntodo = ntodo0 > C.todo_cap ? C.todo_cap : ntodo0;
     if (ntodo) {
       const uint32_t g0 = LC_CTX(c).B->read_begin[S.w];
       LC_GLOBAL uint32_t *mark = W.bitmap;

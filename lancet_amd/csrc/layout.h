@@ -127,6 +127,8 @@ struct EngineCaps {
   uint32_t bx_cap;       /* barcode ids (u32) of the variants' barcode sets, whole batch (lr_mode)   */
   uint32_t wide_ids;     /* work space laid out for the re-run tier's 64-bit csr words / mate-name records (read ids above 16 bits) */
   uint32_t max_w;        /* longest window reference of the batch, rounded up (>= LC_MAXW_DEFAULT, <= LC_MAXW): sizes the alignment / coverage arrays */
+  uint32_t todo_cap;     /* occurrences the mate-overlap prefilter may flag: table_cap in tier 1 (todo[] doubles as the slot -> node table), in the
+                            re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
   struct PreLayout pl;   /* hand-off areas of the LDS build kernel (below)                           */
 };
 
@@ -280,7 +282,7 @@ struct Work {
   LC_GLOBAL uint32_t *occ;          /* [occ_cap]     slot (then node) | ori<<31                           */
   LC_GLOBAL uint32_t *slots;        /* [4*table_cap] k-mer table, 16 bytes per slot: tag (u64), first occurrence, node id */
   LC_GLOBAL uint32_t *mv;           /* [4*occ_cap] mate-name vectors of the nodes with flagged occurrences (read << 16 | name rank); wide_ids: [8*occ_cap], 64-bit records */
-  LC_GLOBAL uint32_t *todo;         /* [table_cap] occurrences flagged by the mate-overlap prefilter (read << 10 | position)  */
+  LC_GLOBAL uint32_t *todo;         /* [todo_cap >= table_cap] node id per slot, then the occurrences flagged by the mate-overlap prefilter (read << 10 | position) */
   LC_GLOBAL unsigned long long *slot_key; /* [table_cap * LC_NWMAX]                                    */
   LC_GLOBAL uint32_t *bitmap;       /* [occ_cap/32 + 2]                                                  */
   LC_GLOBAL uint32_t *bitpre;       /* [occ_cap/32 + 2]                                                  */
