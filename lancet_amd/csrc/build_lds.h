@@ -20,7 +20,10 @@
 // window outside the limits below run the general build phases of kernels.h.  Nothing is approximated: a window either gets
 // the identical node table here or is marked PB_NOT_BUILT.
 //
-// Not handled here (-> PB_NOT_BUILT, general path): --linked-reads, N in the window reference, even k or k > 31, windows
+// N in the window reference: the LDS copy stays 2 bits per base with one bit per base beside it (the N mask); the N k-mers of the
+// pseudo-read are nodes named by their string, settled in a pass of their own after the in-band node ids (build_lds_impl.h, `hasN`).
+//
+// Not handled here (-> PB_NOT_BUILT, general path): even k, windows
 // above the LDS limits, windows with an occurrence the mate-overlap prefilter flags (hasOverlappingMate needs the replay of
 // build_csr), reads whose name occurs more than once with the same mate number.
 #pragma once
@@ -51,7 +54,7 @@
 #else
 #define BL_TAIL_PRIO_SET(p) ((void)0)
 #endif
-enum { BLW_NONE = 0, BLW_NOREADS, BLW_SIZE, BLW_HASN, BLW_K, BLW_TABLE, BLW_NODES, BLW_TRACKED, BLW_CAND, BLW_QV, BLW_SURV, BLW_MATE, BLW_NAMES, BLW_PAIRS,
+enum { BLW_NONE = 0, BLW_NOREADS, BLW_SIZE, BLW_HASN /* (no longer set: windows with N are built; kept for the numbers of the others) */, BLW_K, BLW_TABLE, BLW_NODES, BLW_TRACKED, BLW_CAND, BLW_QV, BLW_SURV, BLW_MATE, BLW_NAMES, BLW_PAIRS,
        BLW_KBIG /* k > 31: the 1024-lane configuration's (keys of up to four words) */ };
 
 #ifdef LANCET_WAVE_EMU

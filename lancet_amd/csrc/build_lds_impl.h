@@ -69,6 +69,7 @@ struct BlScratch {
   LC_GLOBAL uint32_t *pq;           /* [BL_PQCAP] per-position counts: the occurrences of the candidates beyond the first LDS group (read | position << 10 | candidate << 20 | reversed << 31) */
 };
 static constexpr uint32_t BL_PQCAP = 16384u;
+static constexpr uint32_t BL_NMW = LC_MAXW / 32;    /* words of the N mask of a window reference (one bit per base) */
 static constexpr uint32_t SCRATCH_BYTES = (((uint32_t)sizeof(bl_on_t) * BL_BASES + 64u + (BL_WIDE ? 4u * BL_NCAP + 64u : 64u) + 8u * BL_TCAP + 4u * BL_TCAP + 12u * PB_CCAP + 4u * PB_SCAP + 36u * PB_SCAP + (uint32_t)sizeof(bl_off_t) * BL_DUPCAP + 16u * PB_CMAX + 4u * 16384u + 768u) + 255u) & ~255u;   /* (a multiple of 256: the strips' 16-byte loads stay aligned in every slot) */
 static constexpr int WG = BL_WG;
 DEV void bl_scratch_carve(BlScratch *s, LC_GLOBAL uint8_t *base) {
@@ -291,6 +292,28 @@ DEV bool bl_all_good(const LC_LDS uint32_t *goodm, uint32_t gw, int a, int b) {
   return true;
 }
 
+// ---- windows whose reference contains N (kernels.h nk_char states the rule).  The LDS copy of the reference stays 2 bits per
+// base (an N reads as A there); one bit per reference base beside it says where the N are.  A k-mer start of the pseudo-read whose k bases
+// touch a set bit is an "N start": its k-mer is a node of its own, named by its string, that no read ever meets.
+DEV bool bl_nbit(const LC_LDS uint32_t *nm, int i) { return ((nm[(uint32_t)i >> 5] >> ((uint32_t)i & 31u)) & 1u) != 0; }
+DEV bool bl_nstart(const LC_LDS uint32_t *nm, int p, int K) {              // an N among the bases [p, p + K)
+  for (int i = p; i < p + K;) {
+    const int lo = i & 31;
+    int take = 32 - lo; if (take > p + K - i) take = p + K - i;
+    uint32_t m = nm[(uint32_t)i >> 5] >> lo;
+    if (take < 32) m &= (1u << take) - 1u;
+    if (m) return true;
+    i += take;
+  }
+  return false;
+}
+// the canonical string of the N k-mer at reference offset p (CanonicalMer_t::set with N <-> N, A < C < G < N < T, tie -> R): character j as a code 0..4
+DEV int bl_nk_char(LC_GLOBAL const uint8_t *ref, int p, int K, bool isR, int j) { const int c = isR ? (int)ref[p + K - 1 - j] : (int)ref[p + j]; const int d = c > 3 ? 4 : c; return isR ? n_comp(d) : d; }
+DEV bool bl_nk_forward(LC_GLOBAL const uint8_t *ref, int p, int K) {
+  for (int j = 0; j < K; ++j) { const int a = n_ord(bl_nk_char(ref, p, K, false, j)), b = n_ord(bl_nk_char(ref, p, K, true, j)); if (a != b) return a < b; }
+  return false;
+}
+
 // a growth stage of the table order, first pass: bucket of every element under B buckets, smallest position per bucket (stamped: see the stages);
 // U = elements per lane (n <= U * BL_WG <= 4096), all of a lane's look-ups in flight together
 template <int U> DEV void bl_stage_buckets(const LC_LDS uint16_t *Q, LC_GLOBAL const unsigned long long *nhash, uint32_t n, uint32_t B, uint32_t st,
@@ -363,8 +386,9 @@ DEV void bl_occw_set(BlOccW &w, int j, uint32_t v) {                 // (v < 65 
 #endif
 // every chunk of the window that holds k-mer starts: body(chunk, its eight per-occurrence words).  The words of the lane's NEXT chunk are
 // loaded before this one is worked off (unconditionally, index clamped: a conditional load would wait for every earlier store).
-template <class F> DEV void bl_for_chunk(BL_S &S, LC_GLOBAL const bl_on_t *occn, F body) {
-  const int nr = S.R - 1, NC = (int)S.cbase[nr + 1], reflen = S.reflen, K = S.K;
+// (reads_only: without the chunks of the reference pseudo-read -- a window with N in its reference, whose callers walk that read on their own)
+template <class F> DEV void bl_for_chunk(BL_S &S, LC_GLOBAL const bl_on_t *occn, F body, bool reads_only = false) {
+  const int nr = S.R - 1, NC = (int)S.cbase[reads_only ? nr : nr + 1], reflen = S.reflen, K = S.K;
   WG_FOR(_t, BL_WG) {
     if (_t < NC) {
       BlChunk ch; bl_chunk(S, _t, nr, reflen, K, ch);
@@ -380,10 +404,10 @@ template <class F> DEV void bl_for_chunk(BL_S &S, LC_GLOBAL const bl_on_t *occn,
   }
 }
 // the same walk, one call of `body(r, p, boff, word)` per occurrence
-template <class F> DEV void bl_for_occ(BL_S &S, LC_GLOBAL const bl_on_t *occn, F body) {
+template <class F> DEV void bl_for_occ(BL_S &S, LC_GLOBAL const bl_on_t *occn, F body, bool reads_only = false) {
   bl_for_chunk(S, occn, [&](const BlChunk &ch, const BlOccW &w) {
     for (int j = 0; j < ch.nv; ++j) body(ch.r, ch.p0 + j, ch.boff0 + (uint32_t)j, bl_occw_get(w, j));
-  });
+  }, reads_only);
 }
 // the chunk's bases as a bit string: base i of the chunk (i = 0 .. 8 + K - 2 <= 37 for k <= 31) at bits 2i of (lo, hi)
 DEV void bl_chunk_bases(const LC_LDS uint32_t *bases, int c, unsigned long long &lo, unsigned long long &hi) {
@@ -919,13 +943,15 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   WG_LANE0 {
     S.nbw = nbw; S.ngw = ngw;
     if (S.mapped <= 0) S.why = BLW_NOREADS;                    // the window kernel reports LANCET_W_NO_READS itself
-    else if (S.hasN) S.why = BLW_HASN;
-    else if (nbw > BL_BASES / 16 || ngw > BL_BASES / 32 || S.flagged) S.why = BLW_SIZE;
+    else if (nbw + (S.hasN ? BL_NMW : 0u) > BL_BASES / 16 || ngw > BL_BASES / 32 || S.flagged) S.why = BLW_SIZE;      // (N in the reference: its N mask lies behind the packed reads)
     S.flagged = 0;
   }
   if (bl_bcast(&S.why)) { WG_LANE0 { H->why = (uint32_t)S.why; } return; }
   WG_FOR(r, nr + 2) { S.rdo[r] = (uint16_t)tmpA[r]; S.gwo[r] = (uint16_t)tmpB[r]; }
   WG_SYNC();
+  // Everything a reference with N adds below sits behind this one workgroup-uniform flag (written before the barriers of the scans above).
+  const bool hasN = lc_sgpr((int)S.hasN) != 0;
+  LC_LDS uint32_t *nmask = &S.bases[nbw + 4u];                   // [BL_NMW] hasN: bit i = reference base i is an N (behind the packed reads and their four spare words)
   BLP(S, 1);
   if (C->debug_stop == 101u) { WG_LANE0 { H->why = 99; } return; }
   // ---- the window's packed reads and quality masks into LDS (whole words; a read starts on a word)
@@ -942,13 +968,21 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
     S.bases[S.rdo[nr] + wd] = v;
   }
   WG_FOR(i, 4) { S.bases[nbw + (uint32_t)i] = 0; }
+  if (hasN) {
+    WG_FOR(wd, BL_NMW) {
+      uint32_t v = 0;
+      for (int j = 0; j < 32 && wd * 32 + j < reflen; ++j) v |= (refc[wd * 32 + j] > 3 ? 1u : 0u) << j;
+      nmask[wd] = v;
+    }
+  }
   WG_SYNC();
   BLP(S, 2);
   if (C->debug_stop == 102u) { WG_LANE0 { H->why = 99; } return; }
   // ---- reference repeat scan -> the first k of the loop that reaches buildgraph (Microassembler.cc:118-131)
   if (rep) { WG_LANE0 { S.repE = rep->refE; S.repM = rep->refM; } WG_SYNC(); }
   else repeat_scan_min((volatile LC_LDS unsigned long long *)(S.big + 4 * (BL_RMAX + 8)), refc, reflen, P->max_mismatch, P->min_k, P->min_k + 1, (volatile LC_LDS int *)&S.repE, (volatile LC_LDS int *)&S.repM,
-                  (const LC_LDS uint32_t *)&S.bases[S.rdo[nr]], (volatile LC_LDS int *)&S.flagged);     // (the reference is in LDS already, 2 bits per base: no N here)
+                  hasN ? (const LC_LDS uint32_t *)nullptr : (const LC_LDS uint32_t *)&S.bases[S.rdo[nr]], hasN ? (volatile LC_LDS int *)nullptr : (volatile LC_LDS int *)&S.flagged);
+                  // (the reference is in LDS already, 2 bits per base; with N in it the scan reads the codes instead, four bits per base, as the window kernel's does: N equals N)
   WG_LANE0 {
     int K = 0;
     for (int k = kmin; k <= P->max_k; k += 2) {
@@ -957,7 +991,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
       K = k; break;
     }
     S.K = K;
-    H->refE = S.repE; H->refM = S.repM; H->mapped = (uint32_t)S.mapped; H->have_rep = 1;          // (the window kernel does not repeat the scan)
+    H->refE = S.repE; H->refM = S.repM; H->mapped = (uint32_t)S.mapped; H->hasN = hasN ? 1u : 0u; H->have_rep = 1;          // (the window kernel does not repeat the scan)
     if (K == 0 || (K & 1) == 0) S.why = BLW_K;
     else if (2 * K > 64 * (int)PL.kw) S.why = BLW_K;                     // (the batch's hand-off areas hold one-word keys)
     else if (K > BL_KMAX) S.why = BLW_KBIG;                              // (the 1024-lane configuration takes it off the list)
@@ -1190,6 +1224,28 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   }
 #endif
   if (bl_bcast(&S.why)) { WG_LANE0 { H->why = (uint32_t)S.why; } return; }
+  const int nrefk = reflen - K > 0 ? reflen - K + 1 : 0;            // k-mer starts of the reference pseudo-read
+  const uint32_t rbN = hasN ? 16u * (uint32_t)S.rdo[nr] : 0u;      // LDS offset of its first base (read by the hasN sections only)
+  if (hasN) {
+    // The insert pass knows nothing of N: at an N start it has put the 2-bit image of the k-mer (N read as A) into the table.  That image
+    // is no k-mer of the window unless a read, or an in-band start of the pseudo-read, holds it too.  The pseudo-read is the last read, so
+    // an entry whose first occurrence is an N start has no read on it: its offset goes to the top, the in-band starts of the pseudo-read
+    // put themselves forward again (atomicMin, as in the pass), and what nobody claimed leaves the table -- nothing probes it from here on.
+    // The N starts' own per-occurrence words are rewritten once the N nodes have their ids (below).
+    WG_FOR(i, nslots) {
+      const uint32_t e = tab[i];
+      if (e != BL_EMPTY) { const uint32_t off = e & BL_OFFMASK; if (off >= rbN && off - rbN < (uint32_t)nrefk && bl_nstart(nmask, (int)(off - rbN), K)) tab[i] = e | BL_OFFMASK; }
+    }
+    WG_SYNC();
+    WG_FOR(i, nrefk) {
+      if (bl_nstart(nmask, i, K)) continue;
+      const uint32_t sl = (uint32_t)X.occn[rbN + (uint32_t)i] & (nslots - 1);
+      dev_atomic_min(&tab[sl], (tab[sl] & ~BL_OFFMASK) | (rbN + (uint32_t)i));
+    }
+    WG_SYNC();
+    WG_FOR(i, nslots) { const uint32_t e = tab[i]; if (e != BL_EMPTY && (e & BL_OFFMASK) == BL_OFFMASK) tab[i] = BL_EMPTY; }
+    WG_SYNC();
+  }
   BLP(S, 5);
   if (C->debug_stop == 105u) { WG_LANE0 { H->why = 99; } return; }
   // ---- node ids in first-insertion order: rank of the slot's first-occurrence offset among the occupied slots
@@ -1222,7 +1278,62 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
     }
     WG_SYNC();
   }
-  const uint32_t N = bl_bcast(&S.N);
+  const uint32_t NI = bl_bcast(&S.N);                              // in-band nodes: the k-mers of the reads and of the pseudo-read's in-band starts
+  if (hasN) {
+    // ---- the N nodes.  Every N start's k-mer made canonical as a string and hashed (std::hash over "ACGTN": also what tells two of them
+    //      apart quickly); the same string at two offsets -- as it stands or as its reverse complement -- is one node, which takes its id
+    //      from its first offset: N_inband + rank, since the pseudo-read is loaded after every read.  An N node gets a free slot of the table,
+    //      so that the passes below meet it like any node that no read holds: never tracked, no candidate, no survivor.
+    //      (cidx and t2c are idle here: hashes | first offsets in cidx, orientations and first-flags -> ranks in t2c; every array is written
+    //       by the lane of its own offset only, and never in a pass in which another lane reads it)
+    LC_LDS unsigned long long *nh = (LC_LDS unsigned long long *)S.cidx;       // [LC_MAXW] hash of the N start's k-mer; a node's first offset: its table slot, once it has one
+    LC_LDS uint16_t *nfi = (LC_LDS uint16_t *)(nh + LC_MAXW);                  // [LC_MAXW] first offset that holds the same node
+    LC_LDS uint16_t *nor = S.t2c, *nrk = S.t2c + LC_MAXW;                      // [LC_MAXW] each: 1 = the k-mer lies reversed ; 1 = a node's first offset -> rank among those
+    static_assert(sizeof(S.cidx) >= 10u * LC_MAXW && sizeof(S.t2c) >= 4u * LC_MAXW && BL_SLOTS <= 65536u, "scratch of the N nodes");
+    LC_GLOBAL unsigned long long *nhash = (LC_GLOBAL unsigned long long *)(area + PRE_OFF_NHASH);
+    LC_GLOBAL uint8_t *surv = (LC_GLOBAL uint8_t *)(area + PRE_OFF_SURV);
+    WG_FOR(i, nrefk) {
+      unsigned long long h = 0; bool isR = false;
+      if (bl_nstart(nmask, i, K)) {
+        isR = !bl_nk_forward(refc, i, K);
+        h = std_hash_bytes([&](int j) -> int { return (int)"ACGTN"[bl_nk_char(refc, i, K, isR, j)]; }, K);
+      }
+      nh[i] = h; nor[i] = isR ? 1 : 0; nrk[i] = 0;
+    }
+    WG_SYNC();
+    WG_FOR(i, nrefk) {
+      if (!bl_nstart(nmask, i, K)) continue;
+      const unsigned long long h = nh[i]; const bool isR = nor[i] != 0;
+      int first = i;
+      for (int j = 0; j < i; ++j) {
+        if (nh[j] != h || !bl_nstart(nmask, j, K)) continue;
+        const bool jR = nor[j] != 0;
+        bool same = true;
+        for (int t = 0; t < K && same; ++t) same = bl_nk_char(refc, i, K, isR, t) == bl_nk_char(refc, j, K, jR, t);
+        if (same) { first = j; break; }
+      }
+      nfi[i] = (uint16_t)first;
+      if (first == i) nrk[i] = 1;
+    }
+    bl_scan_t<uint16_t>(nrk, nrefk, S);
+    WG_LANE0 { S.N = NI + S.scan_total; if (NI + S.scan_total > BL_NCAP || NI + S.scan_total > PL.ncap) S.why = BLW_NODES; }
+    if (bl_bcast(&S.why)) { WG_LANE0 { H->why = (uint32_t)S.why; } return; }
+    WG_FOR(i, nrefk) {
+      if (!bl_nstart(nmask, i, K) || (uint32_t)nfi[i] != (uint32_t)i) continue;
+      const uint32_t id = NI + (uint32_t)nrk[i];
+      uint32_t sl = (id * 0x9E3779B1u) >> 7 & (nslots - 1);
+      while (dev_atomic_cas32(&tab[sl], BL_EMPTY, id) != BL_EMPTY) sl = (sl + 1) & (nslots - 1);       // (more slots than nodes: ends)
+      nhash[id] = nh[i]; surv[id] = 0;
+      nh[i] = (unsigned long long)sl;
+    }
+    WG_SYNC();
+    WG_FOR(i, nrefk) {
+      if (!bl_nstart(nmask, i, K)) continue;
+      X.occn[rbN + (uint32_t)i] = (bl_on_t)((uint32_t)nh[nfi[i]] | (nor[i] ? ON_ORI : 0u));      // (slot | orientation, as the insert pass leaves it)
+    }
+    WG_SYNC();
+  }
+  const uint32_t N = hasN ? bl_bcast(&S.N) : NI;                   // (a window without N: the one broadcast above, as ever)
   BLP(S, 6);
   if (C->debug_stop == 106u) { WG_LANE0 { H->why = 99; } return; }
   // ---- pass 2: slot -> node id per occurrence (HBM, streamed), occurrences per node
@@ -1249,7 +1360,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   {
     LC_GLOBAL unsigned long long *nhash = (LC_GLOBAL unsigned long long *)(area + PRE_OFF_NHASH);
     LC_GLOBAL uint8_t *surv = (LC_GLOBAL uint8_t *)(area + PRE_OFF_SURV);
-    WG_FULL_BEGIN(n, act, N)                                     // (every lane hashes: wave.h WG_FULL_BEGIN)
+    WG_FULL_BEGIN(n, act, NI)                                    // (every lane hashes: wave.h WG_FULL_BEGIN; the N nodes have theirs)
       unsigned long long h;
 #if BL_KW > 1
       if (NW > 1) {
@@ -1271,6 +1382,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   const uint32_t tthr = tmin < 2 ? (uint32_t)tmin : 2u;
   WG_FOR(i, nslots) { const uint32_t e = tab[i]; if (e != BL_EMPTY) S.cidx[e & 0xFFFFu] = (uint16_t)(e >> 16); }     // count by node id
   WG_SYNC();
+  if (hasN) { WG_FOR(n, N - NI) { S.cidx[NI + (uint32_t)n] = 0; } WG_SYNC(); }      // (an N node is never tracked, however often the pseudo-read holds it)
   {   // the hint's occurrences: only nodes with real coverage matter (a hairpin in one erroneous read survives removeLowCov
       // with coverage 2 and is trimmed as a tip later: k is not rejected for it)
     const uint32_t nd = S.ndup < BL_DUPCAP ? S.ndup : BL_DUPCAP;
@@ -1812,9 +1924,24 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   // ---- trace only: edge count of every node before the filter (printStats over the whole table): distinct (side, base) slots
   if (C->evt_cap) {
     LC_LDS uint32_t *msk = S.big + BL_NCAP / 32;                   // one byte per node, four nodes per word
+    // (N in the reference: a step of the pseudo-read can extend a node by an N -- a slot of its own on either side, kernels.h build_gather's
+    //  edge classes 8 and 9 -- two more bits per in-band node and ten slots per N node, set by a walk over the pseudo-read on its own)
+    LC_LDS uint32_t *msk2 = msk + BL_NCAP / 4, *mskn = msk2 + BL_NCAP / 16;      // [BL_NCAP / 16] two bits per node ; [LC_MAXW] per N node
+    static_assert(4u * (BL_NCAP / 32 + BL_NCAP / 4 + BL_NCAP / 16 + LC_MAXW) <= (uint32_t)BL_BIG, "edge slots of a window with N");
     WG_FOR(i, BL_NCAP / 4) { msk[i] = 0; }
+    if (hasN) { WG_FOR(i, BL_NCAP / 16 + LC_MAXW) { msk2[i] = 0; } }
     WG_LANE0 { S.edges_total = 0; }
     WG_SYNC();
+    if (hasN) {
+      WG_FOR(i, nrefk) {
+        const uint32_t e = X.occn[rbN + (uint32_t)i], n = e & ON_ID, ori = (e >> ON_ORISH) & 1u;
+        uint32_t m = 0;
+        if (i + 1 < nrefk) { const int b = bl_nbit(nmask, i + K) ? 4 : bl_base(S.bases, rbN + (uint32_t)(i + K)); const int eb = ori == 0 ? b : n_comp(b); m |= 1u << (eb < 4 ? (ori == 0 ? 0 : 4) + eb : (ori == 0 ? 8 : 9)); }
+        if (i > 0) { const int b = bl_nbit(nmask, i - 1) ? 4 : bl_base(S.bases, rbN + (uint32_t)(i - 1)); const int eb = ori == 0 ? b : n_comp(b); m |= 1u << (eb < 4 ? (ori == 0 ? 4 : 0) + eb : (ori == 0 ? 9 : 8)); }
+        if (n >= NI) { if (m) dev_atomic_or(&mskn[n - NI], m); }
+        else { if (m & 0xFFu) dev_atomic_or(&msk[n >> 2], (m & 0xFFu) << (8u * (n & 3u))); if (m >> 8) dev_atomic_or(&msk2[n >> 4], (m >> 8) << (2u * (n & 15u))); }
+      }
+    }
     bl_for_occ(S, X.occn, [&](int r, int p, uint32_t boff, uint32_t e) {
       const uint32_t n = e & ON_ID, ori = (e >> ON_ORISH) & 1u;
       const int tlen = r < nr ? (int)RI_TLEN(S.rinfo[r]) : reflen;
@@ -1823,9 +1950,10 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
       if (p + 1 < nk) { const int b = bl_base(S.bases, boff + (uint32_t)K); m |= 1u << ((ori == 0 ? 0 : 4) + (ori == 0 ? b : 3 - b)); }
       if (p > 0) { const int b = bl_base(S.bases, boff - 1u); m |= 1u << ((ori == 0 ? 4 : 0) + (ori == 0 ? b : 3 - b)); }
       if (m) dev_atomic_or(&msk[n >> 2], m << (8u * (n & 3u)));
-    });
+    }, hasN);
     WG_SYNC();
     WG_FOR(i, (N + 3) / 4) { const uint32_t m = msk[i]; if (m) dev_atomic_add((LC_LDS uint32_t *)&S.edges_total, (uint32_t)dev_popc(m)); }
+    if (hasN) { WG_FOR(i, BL_NCAP / 16 + LC_MAXW) { const uint32_t m = msk2[i]; if (m) dev_atomic_add((LC_LDS uint32_t *)&S.edges_total, (uint32_t)dev_popc(m)); } }
     WG_SYNC();
   }
   BLP(S, 14);
@@ -1868,7 +1996,22 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
             dev_atomic_min(&E[(si - s0) * 8u + sl], 2u * (boff - 1u) + 1u);
           }
         }
-      });
+      }, hasN);
+      if (hasN) {                                                      // the pseudo-read's steps between in-band k-mers (a step into or out of an N node is no survivor's edge)
+        WG_FOR(i, nrefk) {
+          if (bl_nstart(nmask, i, K)) continue;
+          const uint32_t boff = rbN + (uint32_t)i, e = X.occn[boff], si = S.cidx[e & ON_ID], ori = (e >> ON_ORISH) & 1u;
+          if (si < s0 || si >= s1) continue;
+          if (i + 1 < nrefk && !bl_nbit(nmask, i + K)) {
+            const int b = bl_base(S.bases, boff + (uint32_t)K);
+            dev_atomic_min(&E[(si - s0) * 8u + (ori == 0 ? 0u : 4u) + (uint32_t)(ori == 0 ? b : 3 - b)], 2u * boff);
+          }
+          if (i > 0 && !bl_nbit(nmask, i - 1)) {
+            const int b = bl_base(S.bases, boff - 1u);
+            dev_atomic_min(&E[(si - s0) * 8u + (ori == 0 ? 4u : 0u) + (uint32_t)(ori == 0 ? b : 3 - b)], 2u * (boff - 1u) + 1u);
+          }
+        }
+      }
       WG_SYNC();
       WG_FOR(sg, s1 - s0) {                                          // one lane per survivor: its record
         const uint32_t si = s0 + (uint32_t)sg, ci = X.s_ci[si], n = X.c_id[ci], ti = X.c_ti[ci];

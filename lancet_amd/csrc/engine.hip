@@ -1278,7 +1278,7 @@ int lancet_engine_build_phase_times(lancet_engine *e, const unsigned long long *
   *ticks = e->blphase;
   return LANCET_OK;
 }
-// windows of the last run whose first graph came from the LDS build kernel
+// windows of the last run whose first graph came from the LDS build kernel (windows with N in their reference among them)
 int lancet_engine_prebuilt_count(lancet_engine *e) { return e ? e->n_prebuilt : -1; }
 
 // test/tuning hook: the hand-off headers of the last run (status | why << 8 | table order and components came along << 16, K, heavy, N, nsurv, numcomp, ncand, next per window)

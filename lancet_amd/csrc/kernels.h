@@ -5826,7 +5826,7 @@ DEV void process_window(Ctx &c, int w, int rq = -1) {
     WG_SYNC();
   }
   LC_GLOBAL const PreHdr *H0 = LC_CTX(c).OUT->pre ? (LC_GLOBAL const PreHdr *)(LC_CTX(c).OUT->pre + (size_t)w * PRE_STRIDE + PRE_OFF_HDR) : nullptr;
-  WG_LANE0 { S.tmp1 = (H0 && H0->have_rep == 1u) ? 1 : 0; if (S.tmp1) { S.tmp0 = (int)H0->mapped; S.hasN = 0; } }     // (the build kernel counted them; it scans no window with N)
+  WG_LANE0 { S.tmp1 = (H0 && H0->have_rep == 1u) ? 1 : 0; if (S.tmp1) { S.tmp0 = (int)H0->mapped; S.hasN = H0->hasN ? 1 : 0; } }     // (the build kernel counted them and looked for N)
   if (!wg_bcast(&S.tmp1)) {                                     // mapped reads, N in the window reference: all lanes
     WG_SYNC();
     const uint32_t r0 = B.read_begin[w]; const int nr = S.R - 1, rl = S.reflen;

@@ -191,7 +191,7 @@ struct CmpRec {
  * leaves here exactly what the graph phases read: the node table in first-insertion order reduced to what is observable
  * (std::hash of every k-mer for the libstdc++ iteration order, survivor flags), dense records of the nodes that survive the
  * first removeLowCov, their per-position quality counts, the reference pseudo-read's node per offset and the reference
- * coverage.  A window the LDS limits do not hold (or that needs the mate-overlap replay, N handling, even k, k > 31) is marked
+ * coverage.  A window the LDS limits do not hold (or that needs even k) is marked
  * PB_NOT_BUILT and takes the general path (build phases of kernels.h in HBM). */
 #define PB_NCAP 5632          /* distinct k-mers per window of the narrow hand-off (512-lane build: LDS table of 8192 slots) */
 #define PB_NCAP_WIDE 14336    /* ... of the wide one (1024-lane build: 16384 slots)                             */
@@ -222,7 +222,8 @@ struct PreHdr {
   uint32_t lr;                /* --linked-reads: the occurrences of the tracked nodes came along (PRE_OFF_LRNOCC / PRE_OFF_LRCSR): the window kernel replays
                                  barcodes and haplotypes over them (kernels.h load_prebuilt_lr) instead of building the window in HBM    */
   uint32_t lr_total;          /* ... csr entries                                                                    */
-  uint32_t pad[7];
+  uint32_t hasN;              /* the window reference holds an N (valid with have_rep): the general build of a later k needs to know */
+  uint32_t pad[6];
 };
 /* The area's layout is fixed per engine upload, not per build: the front (header, reference arrays) is the same everywhere, the
  * arrays behind it are sized by three numbers the host picks for the batch (host_common.h lc_pre_layout) -- `ncap` distinct k-mers
