@@ -21,6 +21,7 @@
 #ifndef LANCET_ENGINE_H
 #define LANCET_ENGINE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -196,6 +197,92 @@ int lancet_engine_upload_packed(lancet_engine *e, const lancet_window_batch *b, 
  * trimmed length).  label / strand / mate / mapped as in lancet_window_batch. */
 void lancet_pack_read(const lancet_params *P, const char *seq, const char *qual, int len, uint8_t label, uint8_t strand, uint8_t mate, uint8_t mapped,
                       uint32_t *rinfo, uint32_t *bases, uint32_t *good);
+
+/* ---- device read selection (opt-in) -------------------------------------------------------------------------
+ * The alignments of a scan are handed over ONCE (lancet_alignment_table -> lancet_device_reads); a batch is then a list of windows
+ * (lancet_window_slice) and lancet_engine_upload_windows picks every window's reads on the device: the rules of extractReads /
+ * isActiveRegion (reference src/Microassembler.cc:253-655) over per-alignment values that do not depend on the window.
+ * lancet_host_alignment_table / lancet_host_windows (lancet_host.h) produce the two structs from BAMs; a caller that already holds decoded
+ * alignments fills them itself.  All arrays are caller-owned and read-only during the calls. */
+#define LANCET_NOT_TAKEN       1   /* lancet_engine_upload_windows: this batch has to go through lancet_host_batch[_packed] +
+                                      lancet_engine_upload[_packed]; the reason is in lancet_engine_last_error.  Nothing was uploaded. */
+#define LANCET_ALN_SEL_OK 1u       /* lancet_alignment_table::flags: passes every test of extractReads but containment and coverage */
+#define LANCET_ALN_AR_OK  2u       /* ... passes isActiveRegion's filter (MAPQ, duplicate, l_seq != 0) */
+#define LANCET_EVT_X  0            /* lancet_alignment_table::evt_kind: mismatch (MD or CIGAR X), insertion, deletion, soft clip */
+#define LANCET_EVT_I  1
+#define LANCET_EVT_D  2
+#define LANCET_EVT_SC 3
+typedef struct lancet_alignment_table {
+  uint32_t struct_size;        /* sizeof(lancet_alignment_table) of the caller's header (another layout is refused) */
+  uint32_t n_chroms;
+  uint32_t n_aln[2];           /* alignments of the tumor [0] and of the normal [1]; every per-alignment array holds the tumor's, then the
+                                  normal's, each in coordinate order per contig (the order extractReads walks) */
+  const uint32_t *span;        /* [2][n_chroms][2]: per sample and contig (chr_id of the windows) its alignments [first, last) in the arrays */
+  const int32_t  *pos0;        /* 0-based leftmost position */
+  const int32_t  *ref_len;     /* reference bases covered */
+  const uint32_t *l_seq;       /* untrimmed read length */
+  const uint8_t  *flags;       /* LANCET_ALN_* */
+  const uint32_t *rinfo;       /* trimmed length, sample, strand, mate, mapped: as lancet_pack_read leaves them (0 without LANCET_ALN_SEL_OK) */
+  const uint32_t *evt_off;     /* [n + 1] CSR: the evidence events of isActiveRegion per alignment (none without LANCET_ALN_AR_OK) */
+  const uint8_t  *evt_kind;    /* LANCET_EVT_* */
+  const int32_t  *evt_pos;     /* the position isActiveRegion counts the event at (any int: it may lie past the alignment's end) */
+  const uint32_t *name_off;    /* into names */
+  const char     *names;       /* NUL-terminated read names; 8 readable bytes past the last name */
+  uint64_t names_len;
+  const uint32_t *base_woff;   /* (l_seq + 15) / 16 words of `bases` from here, (l_seq + 31) / 32 words of `good` from good_woff */
+  const uint32_t *good_woff;
+  const uint32_t *bases;       /* n_base_words + 4 words */
+  const uint32_t *good;        /* n_good_words + 1 words */
+  uint32_t n_base_words, n_good_words;
+  int32_t min_qual_trim, min_qual_call;      /* the lancet_params thresholds the reads were trimmed / masked with */
+  uint64_t load_id;            /* which load of the host object this is (0 for a caller's own table): windows of another load are not taken */
+} lancet_alignment_table;
+
+typedef struct lancet_window_slice {
+  uint32_t struct_size;        /* sizeof(lancet_window_slice) */
+  int32_t  n_windows;          /* windows of the range that pass the host-side window filters (empty sequence, isRepeat at max_k) */
+  const int32_t  *widx;        /* [n] index in the tiling */
+  const int32_t  *start, *end; /* [n] Ref_t coordinates (1-based start, the reference's `end`) */
+  const int32_t  *chr_id;      /* [n] */
+  const uint32_t *ref_off;     /* [n + 1] into ref_bases */
+  const char     *ref_bases;
+  uint32_t leak_reads;         /* reads the windows BEFORE the range left in the graph (reference src/Microassembler.cc:83); not 0: not taken */
+  int32_t  host_reason;        /* LANCET_SLICE_* below: why the host side wants this range on the host route (0: no reason) */
+  uint64_t load_id;            /* lancet_alignment_table::load_id the range's alignments belong to */
+} lancet_window_slice;
+#define LANCET_SLICE_RG_FILE    1  /* an --rg-file other than "keep all": isActiveRegion's read-group string is sequential state */
+#define LANCET_SLICE_NOT_LOADED 2  /* batch-by-batch loading: the range's alignments are not the loaded ones (lancet_host_load_range) */
+
+/* per-window result of the selection's first pass (debug / tests: lancet_engine_debug_select) */
+typedef struct lancet_select_summary {
+  uint32_t status;             /* bits 0-1: 0 filtered (no active region), 1 kept, 2 skipped for coverage; bit 2: a selected read is mapped;
+                                  bit 3: the evidence table of the window overflowed (the batch is not taken) */
+  uint32_t reads_t, reads_n;   /* selected reads per sample */
+  uint32_t bases;              /* their untrimmed bases */
+  uint32_t tw16, tw32;         /* sums of (trimmed length + 15) / 16 and (trimmed length + 31) / 32: the LDS build kernel's size test */
+} lancet_select_summary;
+
+typedef struct lancet_device_reads lancet_device_reads;
+/* One device allocation that holds the table (the packed words of both samples in one array); shared by every engine on that device.
+ * LANCET_E_NO_DEVICE without a gfx950 device: there is no CPU path. */
+int  lancet_device_reads_create(int device, const lancet_alignment_table *tab, lancet_device_reads **out);
+void lancet_device_reads_destroy(lancet_device_reads *r);
+uint64_t lancet_device_reads_bytes(const lancet_device_reads *r);
+struct lancet_host_opts;
+/* Makes the engine's batch from the windows of `s` on the device -- the arrays lancet_engine_upload_packed stages, with the per-read
+ * word offsets pointing into `reads` (no read word is copied).  kept[i] = tiled index of batch window i (room for s->n_windows).
+ * LANCET_OK: uploaded, continue with lancet_engine_submit / run.  LANCET_NOT_TAKEN: see above; the cases are --linked-reads, a slice with a
+ * host_reason or a non-empty leak or another load_id, a kept window with reads but no mapped read (the reference's read leak would start
+ * there), a window with more selected reads or evidence positions than the selection kernel's LDS holds. */
+int lancet_engine_upload_windows(lancet_engine *e, lancet_device_reads *reads, const lancet_window_slice *s, const struct lancet_host_opts *o,
+                                 int32_t *kept, int32_t *n_kept);
+/* Test hooks.  lancet_engine_debug_select: the summaries of the last lancet_engine_upload_windows (one per window of the slice, also after
+ * LANCET_NOT_TAKEN).  lancet_engine_debug_batch: the uploaded batch read back from the device: which = 0 chr_id, 1 ref_start, 2 ref_off,
+ * 3 ref_codes, 4 read_begin, 5 rinfo, 6 name_rank, 7 base_woff, 8 good_woff (bytes copied, < 0 on error); 9 / 10: the packed base / quality
+ * words of read `arg` (its length is not known to the batch: `cap` bytes are copied); 11 / 12: the whole packed base / quality arrays the
+ * offsets point into (out == NULL or cap == 0: only the size is returned). */
+int lancet_engine_debug_select(lancet_engine *e, const lancet_select_summary **sum, int32_t *n);
+long long lancet_engine_debug_batch(lancet_engine *e, int which, uint32_t arg, void *out, size_t cap);
 
 /* Runs the whole hot path (self-tuning k loop included) for every uploaded window.  Blocking. */
 int lancet_engine_run(lancet_engine *e);

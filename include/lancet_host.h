@@ -101,6 +101,21 @@ int lancet_host_batch_packed(lancet_host *h, int w_begin, int w_end, const lance
  * lancet_host_load_range: lazy mode only (else a no-op) -- loads, once, what the windows [w_begin, w_end) can select, so that the batch calls
  * inside that range do not load again (the range a rank owns). */
 int lancet_host_load_range(lancet_host *h, int w_begin, int w_end, const lancet_host_opts *o);
+/* ---- device read selection (lancet_engine.h: lancet_device_reads, lancet_engine_upload_windows) ----
+ * lancet_host_alignment_table: what is loaded, as a table -- tumor sample then normal sample, each in file order.  Per alignment: geometry,
+ * the values extractReads derives from it whatever the window (strand, mate, mapped: in rinfo), the two filter bits for `o` (with the
+ * tumor / normal asymmetries of the reference in them), the evidence events of isActiveRegion (parseMD + the CIGAR walk, once), the name,
+ * and the read trimmed and packed by the pack cache for `P`'s thresholds (on the host threads; only alignments with LANCET_ALN_SEL_OK).
+ * The arrays are owned by the host object and stay valid until the next call of this function, a reload or lancet_host_close. */
+int lancet_host_alignment_table(lancet_host *h, const lancet_host_opts *o, const lancet_params *P, lancet_alignment_table *tab);
+/* The windows of [w_begin, w_end) that pass the host-side window filters, and what the windows before the range left in the graph
+ * (worked out again when the call does not continue the previous one).  Does not advance the host object: the same range can still go
+ * through lancet_host_batch[_packed].  Arrays owned by the host object, valid until the next lancet_host_windows. */
+int lancet_host_windows(lancet_host *h, int w_begin, int w_end, const lancet_host_opts *o, lancet_window_slice *slice);
+/* The range was assembled by lancet_engine_upload_windows (LANCET_OK): advances the host object past it, with nothing left in the graph
+ * (the device route takes no range that leaves reads there).  LANCET_E_STATE when the range is not the one lancet_host_windows last returned. */
+int lancet_host_windows_done(lancet_host *h, int w_begin, int w_end);
+
 /* barcode strings of the last batch by bx_rank (linked reads) */
 const char *const *lancet_host_bx_names(const lancet_host *h, uint32_t *n);
 

@@ -52,6 +52,32 @@ class LancetPackedReads(C.Structure):
                 ("read_index", C.POINTER(C.c_uint32)), ("n_distinct", C.c_uint32), ("reserved2", C.c_uint32)]
 
 
+# ---- device read selection (include/lancet_engine.h)
+LANCET_NOT_TAKEN = 1
+ALN_SEL_OK, ALN_AR_OK = 1, 2
+
+
+class LancetAlignmentTable(C.Structure):
+    """lancet_alignment_table: the alignments of a scan, handed to the device once (lancet_device_reads_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_chroms", C.c_uint32), ("n_aln", C.c_uint32 * 2),
+                ("span", C.POINTER(C.c_uint32)), ("pos0", C.POINTER(C.c_int32)), ("ref_len", C.POINTER(C.c_int32)), ("l_seq", C.POINTER(C.c_uint32)),
+                ("flags", C.POINTER(C.c_uint8)), ("rinfo", C.POINTER(C.c_uint32)), ("evt_off", C.POINTER(C.c_uint32)), ("evt_kind", C.POINTER(C.c_uint8)),
+                ("evt_pos", C.POINTER(C.c_int32)), ("name_off", C.POINTER(C.c_uint32)), ("names", C.POINTER(C.c_char)), ("names_len", C.c_uint64),
+                ("base_woff", C.POINTER(C.c_uint32)), ("good_woff", C.POINTER(C.c_uint32)), ("bases", C.POINTER(C.c_uint32)), ("good", C.POINTER(C.c_uint32)),
+                ("n_base_words", C.c_uint32), ("n_good_words", C.c_uint32), ("min_qual_trim", C.c_int32), ("min_qual_call", C.c_int32), ("load_id", C.c_uint64)]
+
+
+class LancetWindowSlice(C.Structure):
+    """lancet_window_slice: the windows of a range that pass the host-side window filters (lancet_host_windows)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_windows", C.c_int32), ("widx", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
+                ("chr_id", C.POINTER(C.c_int32)), ("ref_off", C.POINTER(C.c_uint32)), ("ref_bases", C.POINTER(C.c_char)), ("leak_reads", C.c_uint32),
+                ("host_reason", C.c_int32), ("load_id", C.c_uint64)]
+
+
+class LancetSelectSummary(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("status", "reads_t", "reads_n", "bases", "tw16", "tw32")]
+
+
 class LancetVariantLR(C.Structure):
     _fields_ = [("hp", C.c_uint16 * 12), ("bx_off", C.c_uint32 * 4), ("bx_len", C.c_uint32 * 4), ("reserved", C.c_uint32 * 2)]
 

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "kernels.h"
 #include "build_lds.h"
 #include "host_common.h"
+#include "select_host.h"
 
 // window_fat.hip
 extern "C" int lancet_engine_submit(lancet_engine *e);
@@ -231,6 +233,8 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+#include "select_device.h"      // device read selection: the resident table and the two selection kernels
+
 struct lancet_engine {
   lancet_params params;
   int device = 0;
@@ -318,6 +322,10 @@ struct lancet_engine {
   std::vector<lancet_variant_lr> variants_lr;   // lr_mode: parallel to variants
   std::vector<uint32_t> bx_blob;
   float ms_all = 0, ms_kernel = 0;
+  // device read selection (select_device.h): the slice's windows and their summaries on the device, the summaries of the last call
+  DevBuf d_selwin, d_selsum;
+  std::vector<lancet_select_summary> sel_sum;
+  uint64_t n_base_words = 0, n_good_words = 0;      // words readable behind DevBatch::bases / good (lancet_engine_debug_batch)
 };
 
 
@@ -457,7 +465,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   DevBuf *all[] = {&e->d_params, &e->d_batch, &e->d_caps, &e->d_out, &e->d_works, &e->d_chr, &e->d_refstart, &e->d_refoff, &e->d_refasc,
                    &e->d_refcodes, &e->d_readbegin, &e->d_seqoff, &e->d_seq, &e->d_qual, &e->d_label, &e->d_strand, &e->d_mate, &e->d_mapped,
                    &e->d_rinfo, &e->d_name, &e->d_bw, &e->d_gw, &e->d_bases, &e->d_good, &e->d_variants, &e->d_blob, &e->d_counters,
-                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage};
+                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum};
   for (DevBuf *b : all) b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->evb0) (void)hipEventDestroy(e->evb0);
@@ -491,6 +499,8 @@ static int up(lancet_engine *e, DevBuf &b, const void *src, size_t bytes) {
 #define ENS(buf, bytes) do { if ((buf).ensure((bytes) ? (bytes) : 1)) { e->err = "hipMalloc failed"; return LANCET_E_OOM; } } while (0)
 
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk);
+typedef std::function<void(const char *, size_t)> LcTick;
+static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatch &db, const LcTick &tick);
 int lancet_engine_upload(lancet_engine *e, const lancet_window_batch *b) { return lc_upload(e, b, nullptr); }
 // The reads arrive trimmed and packed (lancet_pack_read with THIS engine's parameters: the caller's threads did what the upload's own do
 // from the ASCII arrays); b->seq / qual / label / strand / mate / mapped are not looked at, b->seq_off still gives the untrimmed lengths.
@@ -515,6 +525,43 @@ void lancet_pack_read(const lancet_params *P, const char *seq, const char *qual,
   for (uint32_t wv = (tl + 15) / 16; wv < ((uint32_t)len + 15) / 16; ++wv) bases[wv] = 0;
   for (uint32_t wv = (tl + 31) / 32; wv < ((uint32_t)len + 31) / 32; ++wv) good[wv] = 0;
 }
+// The work-space caps of both tiers and the layout of the hand-off areas, from the sizes of the batch's windows (host_common.h LcBatchSizes:
+// a host batch's arrays, or the summaries of the device read selection).
+static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
+  const int nw = b.n_windows;
+  // (a window longer than LC_MAXW does not fail the batch: process_window reports it LANCET_W_OVERFLOW on its own and every other
+  //  window is assembled.  A window of more than 65 535 reads -- the reference takes up to MAX_AVG_COV = 10 000x per sample,
+  //  src/Microassembler.cc:491-496 -- overflows the one-wave kernel's 16-bit read ids and runs in the re-run tier, whose csr words and
+  //  mate-name records keep the read in 32 bits (layout.h cs_t); its node tables are then sized for up to 2^20 distinct k-mers
+  //  instead of 65 536, unless LANCET_MAX_NODES says otherwise.)
+  // Tier-1 node limit: from the batch unless LANCET_NODE_CAP1 says otherwise -- a quarter of the mean window's bases as distinct k-mers
+  // (30x/30x: ~2.1 k nodes of 27 k bases), a power of two between 8192 and 16384 (16384 for every batch until round 5: the node-sized
+  // arrays are a third of a slot), and never below what a hand-off area of the LDS build kernel may hold (set further down).
+  uint32_t node_cap1 = e->node_cap1;
+  if (!e->node_cap1_env && nw > 0) {
+    const uint64_t mean_bases = (b.total_bases + b.ref_off[nw]) / (uint64_t)nw;
+    node_cap1 = mean_bases / 4 <= 8192 ? 8192u : 16384u;
+  }
+  e->caps = lc_caps_for_sizes(b, &e->params, e->evt_cap, node_cap1, 1);
+  const uint32_t nodes2 = lc_tier2_nodes_for_sizes(b, e->max_nodes_limit, !e->max_nodes_env);
+  e->caps2 = lc_caps_for_sizes(b, &e->params, e->evt_cap, nodes2, 2);
+  e->caps2.wide_ids = e->no_fat ? 0u : 1u;                     // (LANCET_NO_FAT: the one-wave kernel re-runs, with its 16-bit limit)
+  e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;
+  e->caps.debug_stop = e->debug_stop;
+  e->caps.table_start = e->caps2.table_start = e->table_start;
+  {   // hand-off areas of the LDS build kernel: narrow or wide (host_common.h lc_pre_layout_for_batch), one per window + the pool
+    const bool use_svc0 = e->svc && e->n_svc_wgs > 0 && !e->debug_stop;
+    const int depth0 = e->ahead_depth_env >= 0 ? e->ahead_depth_env : 6;
+    const size_t n_areas = (size_t)nw + (depth0 > 0 ? (size_t)std::max(64, nw / 4) : 0) + (use_svc0 ? (size_t)std::max(64, nw / 8) : 0);
+    e->caps.pl = e->caps2.pl = lc_pre_layout_for_sizes(b, n_areas, (size_t)20 << 30, e->pre_wide_env, e->params.lr_mode != 0);
+    if (!e->node_cap1_env && e->caps.pl.ncap + 64u > node_cap1) {          // (wide hand-off areas: 14 336 nodes may arrive from the build kernel)
+      const PreLayout pl = e->caps.pl;
+      e->caps = lc_caps_for_sizes(b, &e->params, e->evt_cap, 16384u, 1);
+      e->caps.debug_stop = e->debug_stop; e->caps.table_start = e->table_start; e->caps.pl = pl;
+      e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;
+    }
+  }
+}
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk) {
   if (!e || !b || b->n_windows < 0) return LANCET_E_ARG;
   if (e->submitted) { e->err = "upload while a batch is in flight"; return LANCET_E_STATE; }
@@ -536,38 +583,9 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
   const uint32_t nref = nw ? b->ref_off[nw] : 0;
   e->n_windows = nw; e->n_reads = (int)R;
   if (nw == 0) { e->uploaded = true; return LANCET_OK; }
-  // (a window longer than LC_MAXW does not fail the batch: process_window reports it LANCET_W_OVERFLOW on its own and every other
-  //  window is assembled.  A window of more than 65 535 reads -- the reference takes up to MAX_AVG_COV = 10 000x per sample,
-  //  src/Microassembler.cc:491-496 -- overflows the one-wave kernel's 16-bit read ids and runs in the re-run tier, whose csr words and
-  //  mate-name records keep the read in 32 bits (layout.h cs_t); its node tables are then sized for up to 2^20 distinct k-mers
-  //  instead of 65 536, unless LANCET_MAX_NODES says otherwise.)
-  // Tier-1 node limit: from the batch unless LANCET_NODE_CAP1 says otherwise -- a quarter of the mean window's bases as distinct k-mers
-  // (30x/30x: ~2.1 k nodes of 27 k bases), a power of two between 8192 and 16384 (16384 for every batch until round 5: the node-sized
-  // arrays are a third of a slot), and never below what a hand-off area of the LDS build kernel may hold (set further down).
-  uint32_t node_cap1 = e->node_cap1;
-  if (!e->node_cap1_env && nw > 0) {
-    const uint64_t mean_bases = ((uint64_t)b->seq_off[b->read_begin[nw]] + b->ref_off[nw]) / (uint64_t)nw;
-    node_cap1 = mean_bases / 4 <= 8192 ? 8192u : 16384u;
-  }
-  e->caps = lc_caps_for_batch(b, &e->params, e->evt_cap, node_cap1, 1);
-  const uint32_t nodes2 = lc_tier2_nodes_for_batch(b, e->max_nodes_limit, !e->max_nodes_env);
-  e->caps2 = lc_caps_for_batch(b, &e->params, e->evt_cap, nodes2, 2);
-  e->caps2.wide_ids = e->no_fat ? 0u : 1u;                     // (LANCET_NO_FAT: the one-wave kernel re-runs, with its 16-bit limit)
-  e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;
-  e->caps.debug_stop = e->debug_stop;
-  e->caps.table_start = e->caps2.table_start = e->table_start;
-  {   // hand-off areas of the LDS build kernel: narrow or wide (host_common.h lc_pre_layout_for_batch), one per window + the pool
-    const bool use_svc0 = e->svc && e->n_svc_wgs > 0 && !e->debug_stop;
-    const int depth0 = e->ahead_depth_env >= 0 ? e->ahead_depth_env : 6;
-    const size_t n_areas = (size_t)nw + (depth0 > 0 ? (size_t)std::max(64, nw / 4) : 0) + (use_svc0 ? (size_t)std::max(64, nw / 8) : 0);
-    e->caps.pl = e->caps2.pl = lc_pre_layout_for_batch(b, n_areas, (size_t)20 << 30, e->pre_wide_env, e->params.lr_mode != 0);
-    if (!e->node_cap1_env && e->caps.pl.ncap + 64u > node_cap1) {          // (wide hand-off areas: 14 336 nodes may arrive from the build kernel)
-      const PreLayout pl = e->caps.pl;
-      e->caps = lc_caps_for_batch(b, &e->params, e->evt_cap, 16384u, 1);
-      e->caps.debug_stop = e->debug_stop; e->caps.table_start = e->table_start; e->caps.pl = pl;
-      e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;
-    }
-  }
+  std::vector<uint32_t> wbases_v;
+  const LcBatchSizes sz = lc_sizes_of_batch(b, &wbases_v);
+  lc_upload_caps(e, sz);
   // ---- inputs
   UP(e->d_params, &e->params, sizeof(lancet_params));
   DevBatch db;
@@ -666,6 +684,7 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
       lc_parallel(T, (size_t)go_all, [&](size_t lo, size_t hi, int) { memcpy(h_go + lo, pk->good + lo, 4 * (hi - lo)); });
     }
     h_ri[R] = 0; h_bw[R] = (uint32_t)bo_all; h_gw[R] = (uint32_t)go_all;
+    e->n_base_words = bo_all + 4; e->n_good_words = go_all + 1;
     for (int i = 0; i < 4; ++i) h_ba[bo_all + (uint64_t)i] = 0;
     h_go[go_all] = 0;
     uint8_t *h_rc = (uint8_t *)(H + o_rc);
@@ -724,6 +743,7 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
   UP(e->d_gw, gw.data(), sizeof(uint32_t) * (R + 1));
   ENS(e->d_bases, sizeof(uint32_t) * (bo + 4));   /* (the occurrence-major insert reads up to two words past a k-mer) */ ENS(e->d_good, sizeof(uint32_t) * (go + 1)); ENS(e->d_rinfo, sizeof(uint32_t) * (R + 1));
   ENS(e->d_refcodes, nref + 1);
+  e->n_base_words = (uint64_t)bo + 4; e->n_good_words = (uint64_t)go + 1;
   DBG("prep launch");
   // ---- prep on the device: Graph_t::trim + packing, reference -> codes
   if (R) hipLaunchKernelGGL(prep_kernel, dim3((R + 3) / 4), dim3(256), 0, e->stream, (const lancet_params *)e->d_params.p, (int)R,
@@ -740,6 +760,12 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
   db.bx_rank = e->params.lr_mode ? (LC_GLOBAL const uint32_t *)e->d_bx.p : nullptr; db.hp = e->params.lr_mode ? (LC_GLOBAL const uint8_t *)e->d_hp.p : nullptr;
   }
   tick("inputs (pack + stage + copy)");
+  return lc_upload_rest(e, sz, db, tick);
+}
+
+// Everything of an upload behind the batch's input arrays: the DevBatch itself, work space, outputs, hand-off areas, the build service.
+static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatch &db, const LcTick &tick) {
+  const int nw = b.n_windows;
   UP(e->d_batch, &db, sizeof(db));
   UP(e->d_caps, &e->caps, sizeof(e->caps));
   UP(e->d_caps2, &e->caps2, sizeof(e->caps2));
@@ -778,14 +804,14 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
   e->pred.clear(); e->is_pred.assign(nw, 0);
   if (!e->debug_stop && !e->no_fat && !e->no_early_rerun) {
     for (int w = 0; w < nw; ++w) {
-      const uint32_t r0 = b->read_begin[w], r1 = b->read_begin[w + 1];
+      const uint32_t r0 = b.read_begin[w], r1 = b.read_begin[w + 1];
       bool big = r1 - r0 + 1 > e->caps.reads_cap ||      // process_window's first tests: more reads, or more bases, than a tier-1 slot holds
-                 (uint64_t)(b->seq_off[r1] - b->seq_off[r0]) + (b->ref_off[w + 1] - b->ref_off[w]) + 64u > (uint64_t)e->caps.occ_cap;
+                 (uint64_t)b.wbases[w] + (b.ref_off[w + 1] - b.ref_off[w]) + 64u > (uint64_t)e->caps.occ_cap;
       // ... or more than the larger configuration of the LDS build kernel takes (131 040 bases with every read padded to 16, 1024 reads):
       // its graphs would all come from the general build on ONE wave (tens of ms: the tail of the launch); the several-wave kernel of the
       // re-run tier builds them in a few ms, next to everything else
       if (!big && e->prebuild && !e->no_large_build) {
-        const uint64_t raw = (uint64_t)(b->seq_off[r1] - b->seq_off[r0]) + 8ull * (r1 - r0) + (b->ref_off[w + 1] - b->ref_off[w]) + 16u;    // (8: the mean padding)
+        const uint64_t raw = (uint64_t)b.wbases[w] + 8ull * (r1 - r0) + (b.ref_off[w + 1] - b.ref_off[w]) + 16u;    // (8: the mean padding)
         big = raw > (uint64_t)bl_large::LDS_BASES || r1 - r0 > bl_large::LDS_READS;
       }
       if (big) { e->pred.push_back((uint32_t)w); e->is_pred[w] = 1; }
@@ -807,7 +833,7 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
     const bool svc_helps = e->svc && e->n_svc_wgs > 0 && !e->debug_stop && e->svc_help;
     e->n_bslots = std::max(1, std::min(nw, cus * 2 - 2 - (svc_helps ? std::min(e->n_svc_wgs, cus) : 0)));
     if (e->build_slots_env) e->n_bslots = std::min(nw, e->build_slots_env);
-    tick("outputs");
+    tick("outputs", 0);
     ENS(e->d_pre, (size_t)nw * e->caps.pl.stride);
     tick("hand-off areas", (size_t)nw * e->caps.pl.stride);
     ENS(e->d_blscratch, (size_t)((e->build_cycle && e->gate) ? std::max(e->n_bslots, 2 * e->n_cus) : e->n_bslots) * bl_small::SCRATCH_BYTES);
@@ -818,8 +844,8 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
     if (e->host_prep && e->exact_need_large >= 0) n_need_large = e->exact_need_large;
     else
     for (int w = 0; w < nw; ++w) {
-      const uint32_t r0 = b->read_begin[w], r1 = b->read_begin[w + 1];
-      const uint64_t raw = (uint64_t)(b->seq_off[r1] - b->seq_off[r0]) + 15ull * (r1 - r0) + (b->ref_off[w + 1] - b->ref_off[w]) + 16u;
+      const uint32_t r0 = b.read_begin[w], r1 = b.read_begin[w + 1];
+      const uint64_t raw = (uint64_t)b.wbases[w] + 15ull * (r1 - r0) + (b.ref_off[w + 1] - b.ref_off[w]) + 16u;
       if (r1 - r0 > bl_small::LDS_READS || raw > (uint64_t)bl_small::LDS_BASES) ++n_need_large;
     }
     may_need_large = n_need_large > 0 || e->caps.pl.kw > 1;      // (wide hand-off areas: windows whose first k is above 31 go to the 1024-lane configuration too)
@@ -852,10 +878,195 @@ static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lance
   UP(e->d_out, &o, sizeof(o));
   DBG("sync");
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  tick("rest + stream sync");
+  tick("rest + stream sync", 0);
   DBG("uploaded");
   e->uploaded = true;
   return LANCET_OK;
+}
+
+// ---- device read selection (include/lancet_engine.h; kernels: select_device.h, rules: select_rules.h, planning: select_host.h) ----
+int lancet_device_reads_create(int device, const lancet_alignment_table *t, lancet_device_reads **out) {
+  if (!t || !out) return LANCET_E_ARG;
+  *out = nullptr;
+  lc_create_err().clear();
+  if (t->struct_size != (uint32_t)sizeof(lancet_alignment_table)) { lc_create_err() = "lancet_alignment_table: struct_size is not this library's (caller built against another header)"; return LANCET_E_ARG; }
+  if (const char *bad = sel_table_check(t); *bad) { lc_create_err() = std::string("lancet_alignment_table: ") + bad; return LANCET_E_ARG; }
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return LANCET_E_NO_DEVICE;      // there is no CPU path
+  if (hipSetDevice(device) != hipSuccess) return LANCET_E_HIP;
+  const size_t N = (size_t)t->n_aln[0] + t->n_aln[1], NE = N ? t->evt_off[N] : 0;
+  struct Part { const void *src; size_t bytes, off; };
+  Part parts[15] = {{t->span, 16 * (size_t)t->n_chroms, 0}, {t->pos0, 4 * N, 0}, {t->ref_len, 4 * N, 0}, {t->l_seq, 4 * N, 0}, {t->flags, N, 0}, {t->rinfo, 4 * N, 0},
+                    {t->evt_off, 4 * (N + 1), 0}, {t->evt_kind, NE, 0}, {t->evt_pos, 4 * NE, 0}, {t->name_off, 4 * N, 0}, {t->names, (size_t)t->names_len + 8, 0},
+                    {t->base_woff, 4 * N, 0}, {t->good_woff, 4 * N, 0}, {t->bases, 4 * ((size_t)t->n_base_words + 4), 0}, {t->good, 4 * ((size_t)t->n_good_words + 1), 0}};
+  if (!N) { parts[6].bytes = 0; parts[10].bytes = 0; }
+  size_t total = 0;
+  for (Part &p : parts) { p.off = total; total = (total + p.bytes + 255) & ~(size_t)255; }
+  lancet_device_reads *r = new lancet_device_reads();
+  r->device = device; r->bytes = total ? total : 256;
+  if (hipMalloc(&r->mem, r->bytes) != hipSuccess) { (void)hipGetLastError(); delete r; lc_create_err() = "hipMalloc failed (resident reads)"; return LANCET_E_OOM; }
+  for (const Part &p : parts) if (p.bytes && hipMemcpy((char *)r->mem + p.off, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    lc_create_err() = std::string("copy of the alignment table: ") + hipGetErrorString(hipGetLastError()); (void)hipFree(r->mem); delete r; return LANCET_E_HIP; }
+  char *D = (char *)r->mem;
+  SelTable &T = r->T;
+  T.n_chroms = t->n_chroms; T.n_aln[0] = t->n_aln[0]; T.n_aln[1] = t->n_aln[1];
+  T.span = (const uint32_t *)(D + parts[0].off); T.pos0 = (const int32_t *)(D + parts[1].off); T.ref_len = (const int32_t *)(D + parts[2].off); T.l_seq = (const uint32_t *)(D + parts[3].off);
+  T.flags = (const uint8_t *)(D + parts[4].off); T.rinfo = (const uint32_t *)(D + parts[5].off); T.evt_off = (const uint32_t *)(D + parts[6].off); T.evt_kind = (const uint8_t *)(D + parts[7].off);
+  T.evt_pos = (const int32_t *)(D + parts[8].off); T.name_off = (const uint32_t *)(D + parts[9].off); T.names = (const char *)(D + parts[10].off);
+  T.base_woff = (const uint32_t *)(D + parts[11].off); T.good_woff = (const uint32_t *)(D + parts[12].off);
+  r->bases = (const uint32_t *)(D + parts[13].off); r->good = (const uint32_t *)(D + parts[14].off);
+  r->n_base_words = (uint64_t)t->n_base_words + 4; r->n_good_words = (uint64_t)t->n_good_words + 1;
+  r->min_qual_trim = t->min_qual_trim; r->min_qual_call = t->min_qual_call; r->load_id = t->load_id;
+  *out = r;
+  return LANCET_OK;
+}
+void lancet_device_reads_destroy(lancet_device_reads *r) {
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  if (r->mem) (void)hipFree(r->mem);
+  delete r;
+}
+uint64_t lancet_device_reads_bytes(const lancet_device_reads *r) { return r ? (uint64_t)r->bytes : 0; }
+
+static int lc_stage_room(lancet_engine *e, size_t total) {
+  if (total <= e->h_stage_cap) return LANCET_OK;
+  if (e->h_stage) (void)hipHostFree(e->h_stage);
+  e->h_stage = nullptr; e->h_stage_cap = 0;
+  const size_t want = total + total / 8;
+  if (hipHostMalloc(&e->h_stage, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); e->err = "hipHostMalloc failed (staging)"; return LANCET_E_OOM; }
+  e->h_stage_cap = want;
+  return LANCET_OK;
+}
+
+int lancet_engine_upload_windows(lancet_engine *e, lancet_device_reads *reads, const lancet_window_slice *s, const lancet_host_opts *o, int32_t *kept, int32_t *n_kept) {
+  if (!e) return LANCET_E_ARG;
+  if (!reads || !s || !o || !kept || !n_kept || s->n_windows < 0) { e->err = "lancet_engine_upload_windows: resident reads, slice, options, kept and n_kept are required"; return LANCET_E_ARG; }
+  if (s->struct_size != (uint32_t)sizeof(lancet_window_slice)) { e->err = "lancet_window_slice: struct_size is not this library's (caller built against another header)"; return LANCET_E_ARG; }
+  if (e->submitted) { e->err = "upload while a batch is in flight"; return LANCET_E_STATE; }
+  if (!e->host_prep) { e->err = "device read selection with LANCET_PREP=device"; return LANCET_E_STATE; }
+  if (reads->device != e->device) { e->err = "the resident reads are on another device than the engine"; return LANCET_E_ARG; }
+  if (reads->min_qual_trim != e->params.min_qual_trim || reads->min_qual_call != e->params.min_qual_call) {
+    e->err = "the resident reads were trimmed / masked with other thresholds than this engine's"; return LANCET_E_ARG; }
+  *n_kept = 0;
+  e->sel_sum.clear();
+  {
+    const std::string why = sel_precheck(reads->load_id, s, o);
+    if (!why.empty()) { e->err = "not taken: " + why; return LANCET_NOT_TAKEN; }
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  e->uploaded = false; e->ran = false;
+  const int n = s->n_windows;
+  if (n == 0) { e->n_windows = 0; e->n_reads = 0; e->uploaded = true; return LANCET_OK; }
+  // ---- pass 1: one summary per window of the slice
+  const size_t win_bytes = (sizeof(SelWin) * (size_t)n + 255) & ~(size_t)255, sum_bytes = sizeof(lancet_select_summary) * (size_t)n;
+  { const int rc = lc_stage_room(e, win_bytes + sum_bytes); if (rc) return rc; }
+  ENS(e->d_selwin, win_bytes); ENS(e->d_selsum, sum_bytes);
+  SelWin *hw = (SelWin *)e->h_stage;
+  for (int i = 0; i < n; ++i) hw[i] = SelWin{s->start[i], s->end[i], s->chr_id[i], s->ref_off[i + 1] - s->ref_off[i]};
+  const SelOpts O = sel_opts_of(o);
+  HIPCHK(e, hipMemcpyAsync(e->d_selwin.p, hw, sizeof(SelWin) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(sel_pass1_kernel, dim3((unsigned)((n + SEL_WAVES - 1) / SEL_WAVES)), dim3(64 * SEL_WAVES), 0, e->stream, reads->T, (const SelWin *)e->d_selwin.p, n, O, (lancet_select_summary *)e->d_selsum.p);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync((char *)e->h_stage + win_bytes, e->d_selsum.p, sum_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  { const lancet_select_summary *hs = (const lancet_select_summary *)((char *)e->h_stage + win_bytes); e->sel_sum.assign(hs, hs + n); }
+  const SelPlan plan = sel_plan(s, e->sel_sum.data(), bl_small::LDS_READS, bl_small::LDS_BASES);
+  if (!plan.reason.empty()) { e->err = "not taken: " + plan.reason; return LANCET_NOT_TAKEN; }
+  const int nk = (int)plan.kslice.size();
+  for (int k = 0; k < nk; ++k) kept[k] = s->widx[plan.kslice[(size_t)k]];
+  *n_kept = nk;
+  if (nk == 0) { e->n_windows = 0; e->n_reads = 0; e->uploaded = true; return LANCET_OK; }
+  const uint32_t R = plan.read_begin[(size_t)nk], nref = plan.ref_off[(size_t)nk];
+  uint64_t total_bases = 0; for (uint32_t b : plan.wbases) total_bases += b;
+  if (total_bases > 0xFFFFFFFFull) { e->err = "not taken: oversize: the batch holds more than 4 Gi bases"; return LANCET_NOT_TAKEN; }
+  const LcBatchSizes sz{nk, plan.read_begin.data(), plan.ref_off.data(), plan.wbases.data(), total_bases};
+  e->n_windows = nk; e->n_reads = (int)R;
+  lc_upload_caps(e, sz);
+  UP(e->d_params, &e->params, sizeof(lancet_params));
+  // ---- the batch: what the host knows goes over in one copy (window arrays, reference codes, which slice window a kept window is);
+  //      the per-read arrays behind it are written by pass 2
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_chr = take(4 * (size_t)nk), o_rs = take(4 * (size_t)nk), o_ro = take(4 * ((size_t)nk + 1)), o_rb = take(4 * ((size_t)nk + 1)), o_ks = take(4 * (size_t)nk), o_rc = take((size_t)nref + 1);
+  const size_t host_part = off;
+  const size_t o_ri = take(4 * ((size_t)R + 1)), o_nm = take(4 * ((size_t)R + 1)), o_bw = take(4 * ((size_t)R + 1)), o_gw = take(4 * ((size_t)R + 1));
+  const size_t total = off;
+  { const int rc = lc_stage_room(e, host_part); if (rc) return rc; }
+  ENS(e->d_stage, total);
+  char *H = (char *)e->h_stage;
+  {
+    int32_t *h_chr = (int32_t *)(H + o_chr), *h_rs = (int32_t *)(H + o_rs), *h_ks = (int32_t *)(H + o_ks);
+    uint8_t *h_rc = (uint8_t *)(H + o_rc);
+    for (int k = 0; k < nk; ++k) { const int i = plan.kslice[(size_t)k]; h_chr[k] = s->chr_id[i]; h_rs[k] = s->start[i]; h_ks[k] = i; }
+    memcpy(H + o_ro, plan.ref_off.data(), 4 * ((size_t)nk + 1)); memcpy(H + o_rb, plan.read_begin.data(), 4 * ((size_t)nk + 1));
+    const int T = e->prep_threads > 0 ? e->prep_threads : e->prep_threads_auto;
+    lc_parallel(T, (size_t)nk, [&](size_t lo, size_t hi, int) {
+      for (size_t k = lo; k < hi; ++k) {
+        const char *src = s->ref_bases + s->ref_off[plan.kslice[k]]; uint8_t *dst = h_rc + plan.ref_off[k];
+        const uint32_t l = plan.ref_off[k + 1] - plan.ref_off[k];
+        for (uint32_t q = 0; q < l; ++q) dst[q] = (uint8_t)lc_code(src[q]);
+      }
+    });
+    h_rc[nref] = 0;
+  }
+  HIPCHK(e, hipMemcpyAsync(e->d_stage.p, e->h_stage, host_part, hipMemcpyHostToDevice, e->stream));
+  char *D = (char *)e->d_stage.p;
+  SelOut out; out.rinfo = (uint32_t *)(D + o_ri); out.name_rank = (uint32_t *)(D + o_nm); out.base_woff = (uint32_t *)(D + o_bw); out.good_woff = (uint32_t *)(D + o_gw);
+  hipLaunchKernelGGL(sel_pass2_kernel, dim3((unsigned)((nk + SEL_WAVES - 1) / SEL_WAVES)), dim3(64 * SEL_WAVES), 0, e->stream, reads->T, (const SelWin *)e->d_selwin.p, (const int32_t *)(D + o_ks),
+                     (const uint32_t *)(D + o_rb), nk, out);
+  HIPCHK(e, hipGetLastError());
+  DevBatch db;
+  db.n_windows = nk;
+  db.chr_id = (LC_GLOBAL const int32_t *)(D + o_chr); db.ref_start = (LC_GLOBAL const int32_t *)(D + o_rs);
+  db.ref_off = (LC_GLOBAL const uint32_t *)(D + o_ro); db.ref_codes = (LC_GLOBAL const uint8_t *)(D + o_rc); db.read_begin = (LC_GLOBAL const uint32_t *)(D + o_rb);
+  db.rinfo = (LC_GLOBAL const uint32_t *)(D + o_ri); db.name_rank = (LC_GLOBAL const uint32_t *)(D + o_nm); db.base_woff = (LC_GLOBAL const uint32_t *)(D + o_bw);
+  db.good_woff = (LC_GLOBAL const uint32_t *)(D + o_gw); db.bases = (LC_GLOBAL const uint32_t *)reads->bases; db.good = (LC_GLOBAL const uint32_t *)reads->good;
+  db.bx_rank = nullptr; db.hp = nullptr;
+  e->n_base_words = reads->n_base_words; e->n_good_words = reads->n_good_words;
+  e->exact_need_large = plan.need_large;
+  return lc_upload_rest(e, sz, db, [](const char *, size_t) {});
+}
+
+int lancet_engine_debug_select(lancet_engine *e, const lancet_select_summary **sum, int32_t *n) {
+  if (!e || !sum || !n) return LANCET_E_ARG;
+  *sum = e->sel_sum.data(); *n = (int32_t)e->sel_sum.size();
+  return LANCET_OK;
+}
+long long lancet_engine_debug_batch(lancet_engine *e, int which, uint32_t arg, void *out, size_t cap) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->uploaded || e->submitted || e->n_windows <= 0) { e->err = "lancet_engine_debug_batch: no uploaded batch at rest"; return LANCET_E_STATE; }
+  HIPCHK(e, hipSetDevice(e->device));
+  DevBatch db;
+  HIPCHK(e, lc_copy(e, &db, e->d_batch.p, sizeof(db), hipMemcpyDeviceToHost));
+  const size_t nw = (size_t)e->n_windows, R = (size_t)e->n_reads;
+  const void *src = nullptr; size_t bytes = 0;
+  uint32_t nref = 0;
+  switch (which) {
+    case 0: src = (const void *)db.chr_id; bytes = 4 * nw; break;
+    case 1: src = (const void *)db.ref_start; bytes = 4 * nw; break;
+    case 2: src = (const void *)db.ref_off; bytes = 4 * (nw + 1); break;
+    case 3: HIPCHK(e, lc_copy(e, &nref, (const char *)db.ref_off + 4 * nw, 4, hipMemcpyDeviceToHost)); src = (const void *)db.ref_codes; bytes = nref; break;
+    case 4: src = (const void *)db.read_begin; bytes = 4 * (nw + 1); break;
+    case 5: src = (const void *)db.rinfo; bytes = 4 * R; break;
+    case 6: src = (const void *)db.name_rank; bytes = 4 * R; break;
+    case 7: src = (const void *)db.base_woff; bytes = 4 * R; break;
+    case 8: src = (const void *)db.good_woff; bytes = 4 * R; break;
+    case 9: case 10: {
+      if (arg >= R) { e->err = "lancet_engine_debug_batch: no such read"; return LANCET_E_ARG; }
+      uint32_t woff = 0;
+      HIPCHK(e, lc_copy(e, &woff, (const char *)(which == 9 ? db.base_woff : db.good_woff) + 4 * (size_t)arg, 4, hipMemcpyDeviceToHost));
+      const uint64_t have = which == 9 ? e->n_base_words : e->n_good_words;
+      if ((uint64_t)woff + cap / 4 > have) { e->err = "lancet_engine_debug_batch: words past the end of the packed array"; return LANCET_E_ARG; }
+      src = (const void *)((which == 9 ? (const uint32_t *)db.bases : (const uint32_t *)db.good) + woff); bytes = cap & ~(size_t)3; break;
+    }
+    case 11: src = (const void *)db.bases; bytes = 4 * (size_t)e->n_base_words; break;
+    case 12: src = (const void *)db.good; bytes = 4 * (size_t)e->n_good_words; break;
+    default: e->err = "lancet_engine_debug_batch: which must be 0 .. 12"; return LANCET_E_ARG;
+  }
+  if (!out || cap == 0) return (long long)bytes;           // (a size query)
+  if (bytes > cap) { e->err = "lancet_engine_debug_batch: " + std::to_string(bytes) + " bytes do not fit the buffer"; return LANCET_E_ARG; }
+  if (bytes) HIPCHK(e, lc_copy(e, out, src, bytes, hipMemcpyDeviceToHost));
+  return (long long)bytes;
 }
 
 // The re-run tier for a list of windows: worst-case work space, window_fat.hip (or the one-wave kernel with LANCET_NO_FAT),

@@ -3,6 +3,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <vector>
 #include "layout.h"
 #include "../../include/lancet_engine.h"
 
@@ -34,45 +35,62 @@ static inline PreLayout lc_pre_layout(uint32_t ncap, uint32_t qvcap, uint32_t kw
 // Which form a batch gets: the wide one (PB_NCAP_WIDE k-mers, keys of 4 words, PB_QVCAP_WIDE rows: windows of 100x / 40x build at
 // k = 31..101 with 9-12 k distinct k-mers) when its windows are deep (more than 400 reads on average: 60x / 60x windows, ~360 reads, all fit the narrow form) and `n_areas` of them stay
 // within `budget` bytes; else the narrow one.  LANCET_PRE_WIDE=0 / 1 forces either (read by the caller, passed as `force`).
-static inline uint32_t lc_max_w_for_batch(const lancet_window_batch *b) {      // EngineCaps::max_w
+// What the sizing below needs of a batch: per window its reads, the untrimmed bases of its reads and its reference length.  A host batch
+// has them in read_begin / seq_off / ref_off (lc_sizes_of_batch); the device read selection has them from its per-window summaries.
+struct LcBatchSizes { int n_windows; const uint32_t *read_begin, *ref_off, *wbases; uint64_t total_bases; };
+static inline LcBatchSizes lc_sizes_of_batch(const lancet_window_batch *b, std::vector<uint32_t> *wbases) {
+  const int nw = b->n_windows > 0 ? b->n_windows : 0;
+  wbases->resize((size_t)nw);
+  for (int w = 0; w < nw; ++w) (*wbases)[(size_t)w] = b->seq_off[b->read_begin[w + 1]] - b->seq_off[b->read_begin[w]];
+  return LcBatchSizes{b->n_windows, b->read_begin, b->ref_off, wbases->data(), nw ? (uint64_t)b->seq_off[b->read_begin[nw]] : 0ull};
+}
+static inline uint32_t lc_max_w_for_sizes(const LcBatchSizes &b) {      // EngineCaps::max_w
   uint32_t m = LC_MAXW_DEFAULT;
-  for (int w = 0; w < b->n_windows; ++w) { const uint32_t l = b->ref_off[w + 1] - b->ref_off[w]; if (l > m && l <= LC_MAXW) m = l; }
+  for (int w = 0; w < b.n_windows; ++w) { const uint32_t l = b.ref_off[w + 1] - b.ref_off[w]; if (l > m && l <= LC_MAXW) m = l; }
   m = (m + 63u) & ~63u;
   return m > LC_MAXW ? (uint32_t)LC_MAXW : m;
 }
-static inline PreLayout lc_pre_layout_for_batch(const lancet_window_batch *b, size_t n_areas, size_t budget, int force = -1, bool lr = false) {
-  const uint32_t mw = lc_max_w_for_batch(b);
+static inline uint32_t lc_max_w_for_batch(const lancet_window_batch *b) { std::vector<uint32_t> wb; return lc_max_w_for_sizes(lc_sizes_of_batch(b, &wb)); }
+static inline PreLayout lc_pre_layout_for_sizes(const LcBatchSizes &b, size_t n_areas, size_t budget, int force = -1, bool lr = false) {
+  const uint32_t mw = lc_max_w_for_sizes(b);
   const PreLayout narrow = lc_pre_layout(PB_NCAP, PB_QVCAP, 1u, mw, lr ? PB_LRCAP : 0u), wide = lc_pre_layout(PB_NCAP_WIDE, PB_QVCAP_WIDE, LC_NWMAX, mw, lr ? PB_LRCAP_WIDE : 0u);
-  if (force == 0 || b->n_windows <= 0) return narrow;
+  if (force == 0 || b.n_windows <= 0) return narrow;
   if (force == 1) return wide;
-  const uint32_t R = b->read_begin[b->n_windows];
-  const bool deep = R / (uint32_t)b->n_windows > 400u;
+  const uint32_t R = b.read_begin[b.n_windows];
+  const bool deep = R / (uint32_t)b.n_windows > 400u;
   return (deep && n_areas * (size_t)wide.stride <= budget) ? wide : narrow;
+}
+static inline PreLayout lc_pre_layout_for_batch(const lancet_window_batch *b, size_t n_areas, size_t budget, int force = -1, bool lr = false) {
+  std::vector<uint32_t> wb; return lc_pre_layout_for_sizes(lc_sizes_of_batch(b, &wb), n_areas, budget, force, lr);
 }
 
 // Node limit of the re-run tier: `limit` (65 536 unless LANCET_MAX_NODES says otherwise), 2^20 when `grow` and a window has 65 535 reads or more.
-static inline uint32_t lc_tier2_nodes_for_batch(const lancet_window_batch *b, uint32_t limit, bool grow) {
-  if (grow) for (int w = 0; w < b->n_windows; ++w) if (b->read_begin[w + 1] - b->read_begin[w] >= 0xFFFFu) return limit > (1u << 20) ? limit : (1u << 20);
+static inline uint32_t lc_tier2_nodes_for_sizes(const LcBatchSizes &b, uint32_t limit, bool grow) {
+  if (grow) for (int w = 0; w < b.n_windows; ++w) if (b.read_begin[w + 1] - b.read_begin[w] >= 0xFFFFu) return limit > (1u << 20) ? limit : (1u << 20);
   return limit;
+}
+static inline uint32_t lc_tier2_nodes_for_batch(const lancet_window_batch *b, uint32_t limit, bool grow) {
+  std::vector<uint32_t> wb; return lc_tier2_nodes_for_sizes(lc_sizes_of_batch(b, &wb), limit, grow);
 }
 // Work-space caps for a batch: the largest window decides.
 // tier 1 = the common case (small tables: cheap to clear, cache/TLB friendly); tier 2 = worst case for the window
 // shapes in the batch, used to re-run the windows that overflowed tier 1.
-static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const lancet_params *p, uint32_t evt_cap,
+static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_params *p, uint32_t evt_cap,
                                            uint32_t max_nodes_limit, int tier = 2) {
+  const LcBatchSizes *b = &bs;
   EngineCaps c; memset(&c, 0, sizeof(c));
   uint32_t max_reads = 0; uint64_t max_bases = 0;
   for (int w = 0; w < b->n_windows; ++w) {
     uint32_t r0 = b->read_begin[w], r1 = b->read_begin[w + 1];
     if (r1 - r0 > max_reads) max_reads = r1 - r0;
-    uint64_t bases = (uint64_t)(b->seq_off[r1] - b->seq_off[r0]) + (b->ref_off[w + 1] - b->ref_off[w]);
+    uint64_t bases = (uint64_t)b->wbases[w] + (b->ref_off[w + 1] - b->ref_off[w]);
     if (bases > max_bases) max_bases = bases;
   }
   if (tier == 1 && b->n_windows > 0) {
     // coverage pile-ups: a window far above the batch's typical size would size every slot's work space; tier 1 is laid
     // out for windows up to 4x the mean (they overflow at once and run in tier 2, whose limits are the true maxima)
     const uint32_t R = b->read_begin[b->n_windows];
-    const uint64_t mean_reads = R / (uint32_t)b->n_windows, mean_bases = ((uint64_t)b->seq_off[R] + b->ref_off[b->n_windows]) / (uint64_t)b->n_windows;
+    const uint64_t mean_reads = R / (uint32_t)b->n_windows, mean_bases = (b->total_bases + b->ref_off[b->n_windows]) / (uint64_t)b->n_windows;
     // (round 5: bases 2x the mean + 16 Ki instead of 4x + 32 Ki -- the occurrence-sized arrays are a third of a slot, and what lies between
     //  is a handful of windows per scan that run in the re-run tier like the pile-ups above them)
     const uint64_t lim_reads = 4 * mean_reads + 256, lim_bases = 2 * mean_bases + 16384;
@@ -106,7 +124,7 @@ static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const l
     { uint64_t q = 4ull * (uint64_t)(p->dfs_limit > 0 ? p->dfs_limit : 1000000) + 4096; if (q < 65536) q = 65536; if (q > (4ull << 20)) q = 4ull << 20; c.queue_cap = (uint32_t)q; }
   }
   c.seq_cap = 3 * c.qv_cap + 65536;
-  c.max_w = lc_max_w_for_batch(b);              // (a window above LC_MAXW is reported LANCET_W_OVERFLOW on its own)
+  c.max_w = lc_max_w_for_sizes(bs);              // (a window above LC_MAXW is reported LANCET_W_OVERFLOW on its own)
   c.path_cap = c.max_w + (uint32_t)p->max_indel_len + 256;
   c.evt_cap = evt_cap;
   // Records of the whole batch.  A scan emits ~0.7 per window; permissive settings (--low-cov 0 on noisy reads) reach several
@@ -118,6 +136,10 @@ static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const l
   c.bx_cap = c.lr_mode ? (uint32_t)b->n_windows * 8192u + (1u << 20) : 0u;
   c.pl = lc_pre_layout(PB_NCAP, PB_QVCAP, 1u, c.max_w);      // (the engine replaces it per upload: lc_pre_layout_for_batch)
   return c;
+}
+static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const lancet_params *p, uint32_t evt_cap,
+                                           uint32_t max_nodes_limit, int tier = 2) {
+  std::vector<uint32_t> wb; return lc_caps_for_sizes(lc_sizes_of_batch(b, &wb), p, evt_cap, max_nodes_limit, tier);
 }
 
 struct LcCarver {

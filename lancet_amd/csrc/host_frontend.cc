@@ -711,6 +711,19 @@ struct lancet_host {
   std::vector<const char *> bx_ptrs;
   // --rg-file (Microassembler::loadRG, reference src/Microassembler.cc:29-48): the read groups to keep; {"null"} keeps everything (:716-721)
   std::set<std::string> readgroups{"null"};
+  // device read selection: the table of the loaded alignments (lancet_host_alignment_table) and the last window slice (lancet_host_windows)
+  uint64_t load_id = 0;             // counts the loads of smp[0] / smp[1]: a table belongs to one of them
+  struct Table {
+    std::vector<uint32_t> span, l_seq, rinfo, evt_off, name_off, bw, gw, bases, good;
+    std::vector<int32_t> pos0, ref_len, evt_pos;
+    std::vector<uint8_t> flags, evt_kind;
+    std::vector<char> names;
+  } tab;
+  std::vector<int32_t> s_widx, s_start, s_end, s_chr;
+  std::vector<uint32_t> s_refoff;
+  std::string s_ref;
+  int s_lo = -1, s_hi = -1;         // the range of the last slice
+  std::vector<int8_t> rep; int rep_k = -1;     // isRepeat per tiled window at max_k = rep_k (-1 not looked at yet): the slices of a scan ask once
 };
 
 namespace {
@@ -719,7 +732,7 @@ inline bool md_valid(char c) { return c != 0 && strchr("acgtumrwsykvhdbxnACGTUMR
 
 // parseMD (reference src/util.cc:428-483) with its quirks: the quality looked at is that of the base after the mismatch
 // in MD coordinates (rpos is incremented first; std::string::operator[] at size() is '\0')
-void parse_md(const char *md, std::unordered_map<int, int> &M, int start, const char *qual, int lqual, int min_qv) {
+template <class Map> void parse_md(const char *md, Map &M, int start, const char *qual, int lqual, int min_qv) {
   const int n = (int)strlen(md);
   auto ffo = [&](int from) { for (int i = from; i < n; ++i) if (md_valid(md[i])) return i; return -1; };
   auto ffno = [&](int from) { for (int i = from; i < n; ++i) if (!md_valid(md[i])) return i; return -1; };
@@ -744,6 +757,27 @@ void parse_md(const char *md, std::unordered_map<int, int> &M, int start, const 
 
 bool any_ge(const std::unordered_map<int, int> &m, int thr) { for (auto &kv : m) if (kv.second >= thr) return true; return false; }
 
+// The evidence of one alignment as isActiveRegion counts it (:300-420): MD mismatches (parseMD) and CIGAR X into mapX, insertions,
+// deletions, soft clips (keyed by the genome position of the S operation).  `pos` advances over every operation but I -- S / H / P included,
+// so an event can lie past the alignment's end.  The maps only need operator[] with a pre-increment: a std::unordered_map for the host
+// route, a list-building sink for lancet_host_alignment_table.
+template <class MX, class MI, class MD, class MS>
+void ar_events(const Sample &S, const Read &r, const lancet_host_opts &o, MX &mapX, MI &mapI, MD &mapD, MS &mapSC) {
+  const int alstart = r.pos0;
+  if (r.has_md) parse_md(S.text.c_str() + r.md_off, mapX, alstart, S.qual.data() + r.seq_off, (int)r.l_seq, o.min_qual_call);
+  int pos = alstart, refpos = alstart;
+  for (uint32_t c = 0; c < r.n_cig; ++c) {
+    const uint32_t cg = S.cigar[r.cig_off + c]; const unsigned op = cg & 15u; const int len = (int)(cg >> 4);
+    if (op != 1) pos += len;
+    if (op == 8) ++mapX[pos];
+    if (op == 1) ++mapI[pos];
+    if (op == 2) ++mapD[pos];
+    // BamAlignment::GetSoftClips (bamtools 2.5.2 src/api/BamAlignment.cpp:536-606): genome position of every S op
+    if (op == 2 || op == 0 || op == 8 || op == 3 || op == 7) refpos += len;
+    else if (op == 4) ++mapSC[refpos];
+  }
+}
+
 // isActiveRegion for one sample (label TMR / NML)
 bool is_active_region(const Sample &S, const Window &win, bool normal, const lancet_host_opts &o, const std::set<std::string> &rgs) {
   const int mq = normal ? 0 : o.min_map_qual;
@@ -764,18 +798,7 @@ bool is_active_region(const Sample &S, const Window &win, bool normal, const lan
     if (r.rg_off != 0xFFFFFFFFu) rg = S.text.c_str() + r.rg_off;       // al.GetTag("RG", rg); if (rg.empty()) rg = "null";  (:296-297)
     if (rg.empty()) rg = "null";
     if (!(rg_all || rgs.count(rg))) continue;                            // :302 (everything below is inside that branch)
-    if (r.has_md) parse_md(S.text.c_str() + r.md_off, mapX, alstart, S.qual.data() + r.seq_off, (int)r.l_seq, o.min_qual_call);
-    int pos = alstart, refpos = alstart;
-    for (uint32_t c = 0; c < r.n_cig; ++c) {
-      const uint32_t cg = S.cigar[r.cig_off + c]; const unsigned op = cg & 15u; const int len = (int)(cg >> 4);
-      if (op != 1) pos += len;
-      if (op == 8) ++mapX[pos];
-      if (op == 1) ++mapI[pos];
-      if (op == 2) ++mapD[pos];
-      // BamAlignment::GetSoftClips (bamtools 2.5.2 src/api/BamAlignment.cpp:536-606): genome position of every S op
-      if (op == 2 || op == 0 || op == 8 || op == 3 || op == 7) refpos += len;
-      else if (op == 4) ++mapSC[refpos];
-    }
+    ar_events(S, r, o, mapX, mapI, mapD, mapSC);
   }
   return any_ge(mapX, o.min_evidence) || any_ge(mapI, o.min_evidence) || any_ge(mapD, o.min_evidence) || any_ge(mapSC, o.min_evidence);
 }
@@ -999,6 +1022,7 @@ int finish_tiling(lancet_host *h, std::map<std::string, std::vector<std::pair<in
   std::thread other(load, 0);                         // the two samples side by side
   load(1);
   other.join();
+  ++h->load_id; h->rep.clear(); h->rep_k = -1; h->s_lo = h->s_hi = -1;
   for (int smp = 0; smp < 2; ++smp) if (!ok[smp]) { h->err = errs[smp]; return LANCET_E_ARG; }
   return (int)h->windows.size();
 }
@@ -1053,6 +1077,7 @@ int reload_for(lancet_host *h, int w_begin, int w_end) {
   std::thread other(load, 0);
   load(1);
   other.join();
+  ++h->load_id;
   for (int smp = 0; smp < 2; ++smp) if (!ok[smp]) { h->err = errs[smp]; return LANCET_E_ARG; }
   return LANCET_OK;
 }
@@ -1466,6 +1491,142 @@ static int host_batch_impl(lancet_host *h, int w_begin, int w_end, const lancet_
   out->name_rank = h->b_namerank.data();
   out->bx_rank = o->linked ? h->b_bxrank.data() : nullptr; out->hp = o->linked ? h->b_hp.data() : nullptr;
   if (n_kept) *n_kept = nk;
+  return LANCET_OK;
+}
+
+}  // extern "C"
+
+// ---- device read selection: the loaded alignments as a table, the windows of a range as a slice (lancet_host.h) ----
+namespace {
+struct Ev { uint8_t kind; int32_t pos; };
+// a "map" for ar_events that lists what it is asked to count
+struct EvSink {
+  std::vector<Ev> *v; uint8_t kind;
+  struct Slot { std::vector<Ev> *v; uint8_t kind; int pos; void operator++() { v->push_back(Ev{kind, (int32_t)pos}); } };
+  Slot operator[](int pos) { return Slot{v, kind, pos}; }
+};
+template <class F> void host_parallel(size_t n, size_t grain, F body) {      // body(lo, hi, t) over a static split of [0, n)
+  const unsigned nt = host_threads((int)std::min<size_t>(n / grain + 1, 1u << 20));
+  if (nt <= 1) { body((size_t)0, n, 0u); return; }
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < nt; ++t) th.emplace_back([=] { body(n * t / nt, n * (t + 1) / nt, t); });
+  body((size_t)0, n / nt, 0u);
+  for (auto &x : th) x.join();
+}
+}  // namespace
+
+extern "C" {
+
+int lancet_host_alignment_table(lancet_host *h, const lancet_host_opts *o, const lancet_params *P, lancet_alignment_table *tab) {
+  if (!h || !o || !P || !tab) { if (h) h->err = "lancet_host_alignment_table: options, parameters and the table struct are required"; return LANCET_E_ARG; }
+  Sample *SS[2] = {&h->smp[1], &h->smp[0]};                       // tumor, then normal
+  const size_t n0 = SS[0]->reads.size(), n1 = SS[1]->reads.size(), N = n0 + n1;
+  const size_t first[2] = {0, n0};
+  for (int s = 0; s < 2; ++s) ensure_pack_cache(*SS[s], *P);
+  const uint64_t bw_all = (uint64_t)SS[0]->pk_bw[n0] + SS[1]->pk_bw[n1], gw_all = (uint64_t)SS[0]->pk_gw[n0] + SS[1]->pk_gw[n1];
+  if (bw_all + 4 > 0xFFFFFFFFull || N + 1 > 0xFFFFFFFFull) { h->err = "more alignments loaded than one table holds (tile fewer windows at a time)"; return LANCET_E_ARG; }
+  lancet_host::Table &T = h->tab;
+  const size_t nc = h->chroms.size();
+  T.span.assign(4 * nc, 0);
+  for (int s = 0; s < 2; ++s) for (size_t c = 0; c < nc; ++c) {       // (a contig this load holds nothing of: an empty span inside the sample)
+    const std::pair<size_t, size_t> sp = c < SS[s]->span.size() ? SS[s]->span[c] : std::pair<size_t, size_t>(0, 0);
+    T.span[(s * nc + c) * 2] = (uint32_t)(first[s] + sp.first); T.span[(s * nc + c) * 2 + 1] = (uint32_t)(first[s] + sp.second); }
+  T.pos0.resize(N); T.ref_len.resize(N); T.l_seq.resize(N); T.flags.resize(N); T.rinfo.resize(N); T.evt_off.assign(N + 1, 0); T.name_off.resize(N);
+  T.bw.resize(N + 1); T.gw.resize(N + 1);
+  T.bases.assign((size_t)bw_all + 4, 0); T.good.assign((size_t)gw_all + 1, 0);
+  const unsigned nt_max = host_threads((int)std::min<size_t>(N / 1024 + 1, 1u << 20));
+  std::vector<std::vector<Ev>> evs(nt_max);
+  std::vector<size_t> ev_lo(nt_max, 0), nm_bytes(nt_max, 0);
+  host_parallel(N, 1024, [&](size_t lo, size_t hi, unsigned t) {
+    std::vector<Ev> &E = evs[t]; ev_lo[t] = lo;
+    size_t nb = 0;
+    for (size_t a = lo; a < hi; ++a) {
+      const int s = a >= n0 ? 1 : 0; const size_t i = a - first[s];
+      Sample &S = *SS[s]; const Read &r = S.reads[i];
+      const bool normal = s == 1;
+      const int mq = normal ? 0 : o->min_map_qual; const double min_delta = normal ? -1 : (double)o->max_delta_as_xs;
+      const bool mapq_ok = r.mapq >= mq && !(r.flag & 0x400);
+      // extract_reads' tests apart from containment and coverage, in its order (:501-579)
+      const bool sel_ok = !(o->primary_alignment_only && (r.flag & 0x100)) && mapq_ok &&
+                          !(std::fabs((double)r.as - (double)r.xs) <= min_delta && r.as != -1.f && r.xs != -1.f) &&
+                          !(r.xt_is_R && !normal) && !(r.has_xa && !normal && o->xa_filter);
+      const bool ar_ok = mapq_ok && r.l_seq != 0;
+      T.pos0[a] = r.pos0; T.ref_len[a] = r.ref_len; T.l_seq[a] = r.l_seq;
+      T.flags[a] = (uint8_t)((sel_ok ? LANCET_ALN_SEL_OK : 0u) | (ar_ok ? LANCET_ALN_AR_OK : 0u));
+      const uint32_t b0 = (uint32_t)((s ? SS[0]->pk_bw[n0] : 0u) + S.pk_bw[i]), g0 = (uint32_t)((s ? SS[0]->pk_gw[n0] : 0u) + S.pk_gw[i]);
+      T.bw[a] = b0; T.gw[a] = g0;
+      uint32_t ri = 0;
+      if (sel_ok) {
+        pack_read_once(S, *P, i);
+        memcpy(&T.bases[b0], (const uint32_t *)S.pk_bases.data() + S.pk_bw[i], 4 * (size_t)((r.l_seq + 15) / 16));
+        memcpy(&T.good[g0], (const uint32_t *)S.pk_good.data() + S.pk_gw[i], 4 * (size_t)((r.l_seq + 31) / 32));
+        const uint8_t mate = (r.flag & 0x40) ? 1 : ((r.flag & 0x80) ? 2 : 0);
+        ri = lc_rinfo_word(S.pk_tlen[i], normal ? LANCET_NML : LANCET_TMR, (r.flag & 0x10) ? LANCET_REV : LANCET_FWD,
+                           ((r.flag & 0x40) && (r.flag & 0x80)) ? 2 : mate, (uint8_t)((r.flag & 0x4) ? 0 : 1));
+      }
+      T.rinfo[a] = ri;
+      const size_t e0 = E.size();
+      if (ar_ok) { EvSink sx{&E, LANCET_EVT_X}, si{&E, LANCET_EVT_I}, sd{&E, LANCET_EVT_D}, sc{&E, LANCET_EVT_SC}; ar_events(S, r, *o, sx, si, sd, sc); }
+      T.evt_off[a + 1] = (uint32_t)(E.size() - e0);              // (counts for now)
+      nb += strlen(S.text.c_str() + r.name_off) + 1;
+    }
+    nm_bytes[t] = nb;
+  });
+  T.bw[N] = (uint32_t)bw_all; T.gw[N] = (uint32_t)gw_all;
+  uint64_t ne = 0;
+  for (size_t a = 0; a < N; ++a) { const uint32_t c = T.evt_off[a + 1]; T.evt_off[a] = (uint32_t)ne; ne += c; }
+  if (ne > 0xFFFFFFFFull) { h->err = "more evidence events than one table holds"; return LANCET_E_ARG; }
+  T.evt_off[N] = (uint32_t)ne;
+  T.evt_kind.resize((size_t)ne); T.evt_pos.resize((size_t)ne);
+  for (unsigned t = 0; t < nt_max; ++t) { size_t q = evs[t].empty() ? 0 : T.evt_off[ev_lo[t]]; for (const Ev &e : evs[t]) { T.evt_kind[q] = e.kind; T.evt_pos[q] = e.pos; ++q; } }
+  size_t nbytes = 0; for (unsigned t = 0; t < nt_max; ++t) nbytes += nm_bytes[t];
+  if (nbytes + 8 > 0xFFFFFFFFull) { h->err = "more read-name bytes than one table holds"; return LANCET_E_ARG; }
+  T.names.assign(nbytes + 8, 0);
+  { size_t q = 0; for (size_t a = 0; a < N; ++a) { const int s = a >= n0 ? 1 : 0; const Sample &S = *SS[s]; const char *nm = S.text.c_str() + S.reads[a - first[s]].name_off;
+                                                   const size_t l = strlen(nm); T.name_off[a] = (uint32_t)q; memcpy(&T.names[q], nm, l); q += l + 1; } }
+  memset(tab, 0, sizeof *tab);
+  tab->struct_size = (uint32_t)sizeof(lancet_alignment_table); tab->n_chroms = (uint32_t)nc; tab->n_aln[0] = (uint32_t)n0; tab->n_aln[1] = (uint32_t)n1;
+  tab->span = T.span.data(); tab->pos0 = T.pos0.data(); tab->ref_len = T.ref_len.data(); tab->l_seq = T.l_seq.data(); tab->flags = T.flags.data(); tab->rinfo = T.rinfo.data();
+  tab->evt_off = T.evt_off.data(); tab->evt_kind = T.evt_kind.data(); tab->evt_pos = T.evt_pos.data(); tab->name_off = T.name_off.data(); tab->names = T.names.data(); tab->names_len = nbytes;
+  tab->base_woff = T.bw.data(); tab->good_woff = T.gw.data(); tab->bases = T.bases.data(); tab->good = T.good.data(); tab->n_base_words = (uint32_t)bw_all; tab->n_good_words = (uint32_t)gw_all;
+  tab->min_qual_trim = P->min_qual_trim; tab->min_qual_call = P->min_qual_call; tab->load_id = h->load_id;
+  return LANCET_OK;
+}
+
+int lancet_host_windows(lancet_host *h, int w_begin, int w_end, const lancet_host_opts *o, lancet_window_slice *sl) {
+  if (!h || !o || !sl || w_begin < 0 || w_end < w_begin || (size_t)w_end > h->windows.size()) { if (h) h->err = "bad window range"; return LANCET_E_ARG; }
+  int reason = 0;
+  if (!h->readgroups.count("null")) reason = LANCET_SLICE_RG_FILE;
+  auto loaded = [&]() { return !h->lazy || (w_begin >= h->loaded_lo && w_end <= h->loaded_hi); };
+  if (!loaded()) reason = reason ? reason : LANCET_SLICE_NOT_LOADED;
+  else if (w_begin != h->next_w) {                    // not the continuation of the call before: what the windows before the range left in the graph
+    const int rc = prime_leak(h, w_begin, o); if (rc != LANCET_OK) return rc;
+    h->next_w = w_begin;                              // (`leak` now belongs to w_begin: a batch call that starts there continues from it)
+    if (!loaded()) reason = reason ? reason : LANCET_SLICE_NOT_LOADED;       // (batch-by-batch loading: working the leak out loaded single windows)
+  }
+  const int n = w_end - w_begin;
+  if (h->rep_k != o->max_k || h->rep.size() != h->windows.size()) { h->rep.assign(h->windows.size(), -1); h->rep_k = o->max_k; }
+  host_parallel((size_t)n, 64, [&](size_t lo, size_t hi, unsigned) {
+    for (size_t i = lo; i < hi; ++i) { int8_t &c = h->rep[(size_t)w_begin + i]; if (c < 0) { const Window &win = h->windows[(size_t)w_begin + i]; c = (win.seq.empty() || is_repeat(win.seq, o->max_k)) ? 1 : 0; } }
+  });
+  h->s_widx.clear(); h->s_start.clear(); h->s_end.clear(); h->s_chr.clear(); h->s_refoff.assign(1, 0); h->s_ref.clear();
+  for (int i = 0; i < n; ++i) if (!h->rep[(size_t)(w_begin + i)]) {
+    const Window &win = h->windows[(size_t)(w_begin + i)];
+    h->s_widx.push_back(w_begin + i); h->s_start.push_back(win.start); h->s_end.push_back(win.end); h->s_chr.push_back(win.chr);
+    h->s_ref += win.seq; h->s_refoff.push_back((uint32_t)h->s_ref.size());
+  }
+  h->s_lo = w_begin; h->s_hi = w_end;
+  memset(sl, 0, sizeof *sl);
+  sl->struct_size = (uint32_t)sizeof(lancet_window_slice); sl->n_windows = (int32_t)h->s_widx.size();
+  sl->widx = h->s_widx.data(); sl->start = h->s_start.data(); sl->end = h->s_end.data(); sl->chr_id = h->s_chr.data(); sl->ref_off = h->s_refoff.data(); sl->ref_bases = h->s_ref.data();
+  sl->leak_reads = reason == LANCET_SLICE_NOT_LOADED ? 0u : (uint32_t)h->leak.size(); sl->host_reason = reason; sl->load_id = h->load_id;
+  return LANCET_OK;
+}
+
+int lancet_host_windows_done(lancet_host *h, int w_begin, int w_end) {
+  if (!h) return LANCET_E_ARG;
+  if (w_begin != h->s_lo || w_end != h->s_hi || h->next_w != w_begin || !h->leak.empty()) { h->err = "lancet_host_windows_done: not the range lancet_host_windows last returned with an empty leak"; return LANCET_E_STATE; }
+  h->next_w = w_end; h->leak.clear(); h->s_lo = h->s_hi = -1;
   return LANCET_OK;
 }
 

@@ -15,6 +15,9 @@
 // Without --rank the program starts the N ranks itself (children of this process, --rank r --rendezvous <path> appended) and waits for
 // them; a job launcher may start the ranks itself with --rank / --rendezvous.  The VCF (rank 0's stdout) does not depend on N.
 // -R / --kmer-recovery: lancet_params::kmer_recovery (not together with --linked-reads: refused before any work is done).
+// --device-select: the loaded alignments are exported once (lancet_host_alignment_table -> lancet_device_reads_create, one table per GPU) and a
+// batch is lancet_host_windows -> lancet_engine_upload_windows -> lancet_host_windows_done; LANCET_NOT_TAKEN batches go through
+// lancet_host_batch_packed -> lancet_engine_upload_packed as without the option.  One stderr line at the end counts both, by reason.
 // Not offered: --print-graph; --num-threads is accepted and ignored (windows are
 // batched on the GPU); -v prints the reference's per-window stage trace to stderr.
 #include "../../include/lancet_host.h"
@@ -47,7 +50,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 int die(const std::string &m) { fprintf(stderr, "lancet_gpu: %s\n", m.c_str()); return 1; }
 void usage() {
@@ -66,6 +69,9 @@ void usage() {
         "                                       on the GPU busy while the next batch is assembled; 32768 is what the kernels alone like best]\n"
         "   --strict                          : write no VCF when a window exceeded the engine's work space (default: finish,\n"
         "                                       list those windows on stderr, exit code 3)\n"
+        "   --device-select                   : the alignments go to the GPU once and every batch's reads are picked there (LANCET_DEVICE_SELECT=1 does\n"
+        "                                       the same); batches the device route does not take -- --linked-reads, --rg-file, reads left in the\n"
+        "                                       graph by a window without mapped reads, oversize windows -- go the usual way; same VCF either way\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -79,6 +85,7 @@ int main(int argc, char **argv) {
   int min_k = 11, max_k = 101, trim_lowqual = 10, min_base_qual = 17, tip_len = 11, cov_thr = 5, low_cov = 1, dfs_limit = 1000000;
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
+  int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
   std::string rendezvous;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
@@ -109,7 +116,7 @@ int main(int argc, char **argv) {
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
-    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1;
+    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -302,6 +309,24 @@ int main(int argc, char **argv) {
   // the rank loads once; the records then reach rank 0 in window order, rank by rank
   const int c_lo = ranked ? (int)((long)nchunks * rank / ranks) : 0, c_hi = ranked ? (int)((long)nchunks * (rank + 1) / ranks) : nchunks;
   if (ranked && c_hi > c_lo && lancet_host_load_range(H, c_lo * step, c_hi * step < nwin ? c_hi * step : nwin, &ho) != LANCET_OK) return die(lancet_host_last_error(H));
+  // --device-select: what is loaded goes to every GPU in use once; a batch is then a list of windows
+  std::map<int, lancet_device_reads *> dev_reads;
+  std::map<std::string, long> not_taken;            // reason (up to its first ':') -> batches
+  long n_taken = 0;
+  if (device_select && packed && !ho.linked) {
+    const double t0 = now();
+    lancet_alignment_table tab;
+    if (lancet_host_alignment_table(H, &ho, &P, &tab) != LANCET_OK) return die(lancet_host_last_error(H));
+    const double t1 = now();
+    for (int d : devs) if (!dev_reads.count(d)) {
+      lancet_device_reads *dr = nullptr;
+      const int rc = lancet_device_reads_create(d, &tab, &dr);
+      if (rc != LANCET_OK) return die(std::string("cannot make the alignments resident on device ") + std::to_string(d) + " (code " + std::to_string(rc) + "): " + lancet_engine_last_error(nullptr));
+      dev_reads[d] = dr;
+    }
+    if (timing) fprintf(stderr, "[lancet_gpu] device select: table of %u + %u alignments exported in %.3f s, %.1f MB resident per GPU after %.3f s\n", tab.n_aln[0], tab.n_aln[1], t1 - t0,
+                        lancet_device_reads_bytes(dev_reads.begin()->second) / 1048576.0, now() - t1);
+  }
   for (int c = 0; c < nchunks; ++c) {
     const int lo = c * step, hi = lo + step < nwin ? lo + step : nwin;
     if (ranked && (c < c_lo || c >= c_hi)) { jobs[(size_t)c].have = true; if (!flush()) return die(fail); continue; }      // another rank's batch
@@ -310,12 +335,30 @@ int main(int argc, char **argv) {
     memset(&PK, 0, sizeof(PK));
     double t0 = now();
     if (sl.fut.valid() && !finish(sl)) return die(fail);          // its kept[] / engine must be free before they are reused
-    if ((packed ? lancet_host_batch_packed(H, lo, hi, &ho, &P, &B, &PK, sl.kept.data(), &nk) : lancet_host_batch(H, lo, hi, &ho, &B, sl.kept.data(), &nk)) != LANCET_OK)
+    const int dev = devs.size() > 1 ? devs[(size_t)c % slots.size() % devs.size()] : devs[0];
+    bool taken = false;
+    if (device_select) {
+      std::string why;
+      if (ho.linked) why = "linked reads";
+      else if (!packed) why = "ASCII hand-over";
+      else {
+        lancet_window_slice SL;
+        if (lancet_host_windows(H, lo, hi, &ho, &SL) != LANCET_OK) return die(lancet_host_last_error(H));
+        t_batch += now() - t0; t0 = now();
+        const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
+        t_engine += now() - t0; t0 = now();
+        if (rc == LANCET_OK) { taken = true; if (lancet_host_windows_done(H, lo, hi) != LANCET_OK) return die(lancet_host_last_error(H)); }
+        else if (rc == LANCET_NOT_TAKEN) { why = lancet_engine_last_error(sl.e); if (why.compare(0, 11, "not taken: ") == 0) why.erase(0, 11); why = why.substr(0, why.find(':')); }
+        else return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+      }
+      if (taken) ++n_taken; else ++not_taken[why];
+    }
+    if (!taken && (packed ? lancet_host_batch_packed(H, lo, hi, &ho, &P, &B, &PK, sl.kept.data(), &nk) : lancet_host_batch(H, lo, hi, &ho, &B, sl.kept.data(), &nk)) != LANCET_OK)
       return die(lancet_host_last_error(H));                      // (overlaps the other engines' kernels)
     t_batch += now() - t0;
     if (nk == 0) { jobs[(size_t)c].have = true; if (!flush()) return die(fail); continue; }
     t0 = now();
-    if ((packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+    if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     t_engine += now() - t0;
     sl.chunk = c; sl.nk = nk; sl.base = done; done += nk; sl.bxn.clear();
     if (ho.linked) { uint32_t nbx = 0; const char *const *bxn = lancet_host_bx_names(H, &nbx); for (uint32_t i = 0; i < nbx; ++i) sl.bxn.emplace_back(bxn[i]); }
@@ -323,7 +366,6 @@ int main(int argc, char **argv) {
     // The launch happens HERE, on the one thread that submits (a few hundred microseconds: everything is asynchronous), behind the kernels
     // of the last engine submitted on the same GPU -- the two batches' kernels run back to back, not side by side; its done-event is
     // recorded by then because its own submit has returned.  Only the wait (re-run tier, read-back) goes to another thread.
-    const int dev = devs.size() > 1 ? devs[(size_t)c % slots.size() % devs.size()] : devs[0];
     lancet_engine *prev = last_on_dev.count(dev) ? last_on_dev[dev] : nullptr;
     t0 = now();
     if (lancet_engine_submit_after(e, prev) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(e));
@@ -334,6 +376,15 @@ int main(int argc, char **argv) {
   }
   for (Slot &sl : slots) if (sl.fut.valid() && !finish(sl)) return die(fail);
   if (!flush()) return die(fail);
+  if (device_select) {
+    std::string line = "[lancet_gpu] device select: " + std::to_string(n_taken) + " batches taken, ";
+    long nn = 0; std::string by;
+    for (auto &kv : not_taken) { nn += kv.second; by += (by.empty() ? "" : ", ") + kv.first + " " + std::to_string(kv.second); }
+    line += std::to_string(nn) + " not taken" + (by.empty() ? "" : " (" + by + ")");
+    if (ranked) line += " [rank " + std::to_string(rank) + "]";
+    fprintf(stderr, "%s\n", line.c_str());
+  }
+  for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
   if (ranked) {
     comm = comm_fut.get();
@@ -377,6 +428,7 @@ int main(int argc, char **argv) {
   std::string cmdline = "lancet";
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
+    if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

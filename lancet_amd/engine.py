@@ -59,6 +59,15 @@ def lib():
         L.lancet_debug_align.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
         L.lancet_debug_align_mode.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
         L.lancet_engine_phase_times.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]
+        # device read selection (opts is host.LancetHostOpts: passed by address)
+        L.lancet_device_reads_create.argtypes = [C.c_int, C.POINTER(abi.LancetAlignmentTable), C.POINTER(C.c_void_p)]
+        L.lancet_device_reads_destroy.argtypes = [C.c_void_p]
+        L.lancet_device_reads_bytes.restype = C.c_uint64
+        L.lancet_device_reads_bytes.argtypes = [C.c_void_p]
+        L.lancet_engine_upload_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.LancetWindowSlice), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.lancet_engine_debug_select.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetSelectSummary)), C.POINTER(C.c_int32)]
+        L.lancet_engine_debug_batch.restype = C.c_longlong
+        L.lancet_engine_debug_batch.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t]
         L.lancet_filters_default.argtypes = [C.POINTER(abi.LancetFilters)]
         L.lancet_vdb_create.restype = C.c_void_p
         L.lancet_vdb_create.argtypes = [C.POINTER(abi.LancetFilters)]
@@ -79,6 +88,33 @@ def lib():
         L.lancet_trace_format.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
         _LIB = L
     return _LIB
+
+
+class DeviceReads:
+    """lancet_device_reads: the alignment table of a scan (host.NativeHost.alignment_table) resident on one device, shared by every
+    engine on it.  There is no CPU path: without a GPU creation raises."""
+
+    def __init__(self, table: "abi.LancetAlignmentTable", device: int = 0):
+        self.L = lib()
+        h = C.c_void_p()
+        rc = self.L.lancet_device_reads_create(device, C.byref(table), C.byref(h))
+        if rc != 0:
+            why = self.L.lancet_engine_last_error(None).decode()
+            raise EngineError(f"lancet_device_reads_create failed: {ERRORS.get(rc, rc)}" + (f" ({why})" if rc not in (-2,) and why != "null engine" else ""))
+        self.h = h
+        self.device = device
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.L.lancet_device_reads_bytes(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lancet_device_reads_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 class Engine:
@@ -123,6 +159,60 @@ class Engine:
         self.L.lancet_engine_upload_packed.restype = C.c_int
         self.L.lancet_engine_upload_packed.argtypes = [C.c_void_p, C.POINTER(abi.LancetWindowBatch), C.POINTER(abi.LancetPackedReads)]
         self._chk(self.L.lancet_engine_upload_packed(self.h, C.byref(cb), C.byref(pk)))
+
+    def upload_windows(self, reads: DeviceReads, slice_, opts, host=None):
+        """lancet_engine_upload_windows: the engine's batch from the windows of `slice_` (host.NativeHost.windows), their reads picked on
+        the device from `reads`.  Returns the tiled indices of the kept windows, or None when the batch is NOT TAKEN and has to go through
+        upload_packed (why: last_error()).  `host` (the NativeHost of the slice) names the windows for trace_text()."""
+        n = max(1, int(slice_.n_windows))
+        kept = (C.c_int32 * n)()
+        nk = C.c_int32()
+        rc = self.L.lancet_engine_upload_windows(self.h, reads.h, C.byref(slice_), C.byref(opts), kept, C.byref(nk))
+        if rc == abi.LANCET_NOT_TAKEN:
+            return None
+        self._chk(rc)
+        idx = [int(kept[i]) for i in range(nk.value)]
+        import types
+        b = types.SimpleNamespace(n_windows=nk.value, hdr=[], chrom=[], ref_start=np.zeros(nk.value, np.int32), ref_off=np.zeros(nk.value + 1, np.uint32))
+        if host is not None:
+            for k, w in enumerate(idx):
+                hdr, chrom, s, e = host.window_info(w)
+                b.hdr.append(hdr); b.chrom.append(chrom); b.ref_start[k] = s; b.ref_off[k + 1] = b.ref_off[k] + (e - s)
+        self._batch = b
+        return idx
+
+    def last_error(self) -> str:
+        return self.L.lancet_engine_last_error(self.h).decode()
+
+    def select_summaries(self):
+        """test hook: the per-window summaries of the last upload_windows (one per window of the slice)."""
+        p = C.POINTER(abi.LancetSelectSummary)()
+        n = C.c_int32()
+        self._chk(self.L.lancet_engine_debug_select(self.h, C.byref(p), C.byref(n)))
+        return [tuple(getattr(p[i], f) for f in ("status", "reads_t", "reads_n", "bases", "tw16", "tw32")) for i in range(n.value)]
+
+    def debug_batch(self):
+        """test hook: the uploaded batch read back from the device, as a dict of arrays (lancet_engine_debug_batch)."""
+        nw = self._batch.n_windows
+        out = {}
+
+        def get(which, count, dt, arg=0):
+            a = np.zeros(max(1, count), dtype=dt)
+            got = self.L.lancet_engine_debug_batch(self.h, which, arg, a.ctypes.data, count * a.itemsize)
+            if got < 0:
+                self._chk(int(got))
+            return a[:got // a.itemsize]
+        out["read_begin"] = get(4, nw + 1, np.uint32)
+        out["ref_off"] = get(2, nw + 1, np.uint32)
+        R = int(out["read_begin"][-1])
+        out["chr_id"] = get(0, nw, np.int32); out["ref_start"] = get(1, nw, np.int32)
+        out["ref_codes"] = get(3, int(out["ref_off"][-1]), np.uint8)
+        for name, which in (("rinfo", 5), ("name_rank", 6), ("base_woff", 7), ("good_woff", 8)):
+            out[name] = get(which, R, np.uint32)
+        out["words"] = lambda r, nb, ng: (get(9, nb, np.uint32, r), get(10, ng, np.uint32, r))      # of one read
+        for name, which in (("bases", 11), ("good", 12)):                                          # the arrays the offsets point into
+            out[name] = get(which, int(self.L.lancet_engine_debug_batch(self.h, which, 0, None, 0)) // 4, np.uint32)
+        return out
 
     def run(self) -> None:
         self._chk(self.L.lancet_engine_run(self.h))

@@ -51,6 +51,10 @@ def _lib():
         L.lancet_host_batch_packed.restype = C.c_int
         L.lancet_host_batch_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LancetHostOpts), C.POINTER(abi.LancetParams), C.POINTER(abi.LancetWindowBatch),
                                                C.POINTER(abi.LancetPackedReads), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.lancet_host_alignment_table.argtypes = [C.c_void_p, C.POINTER(LancetHostOpts), C.POINTER(abi.LancetParams), C.POINTER(abi.LancetAlignmentTable)]
+        L.lancet_host_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LancetHostOpts), C.POINTER(abi.LancetWindowSlice)]
+        L.lancet_host_windows_done.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.lancet_host_load_range.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LancetHostOpts)]
         L.lancet_host_bx_names.restype = C.POINTER(C.c_char_p)
         L.lancet_host_bx_names.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _BOUND = True
@@ -113,6 +117,39 @@ class NativeHost:
 
     def first_has_md(self, tumor: bool) -> bool:
         return bool(self.L.lancet_host_first_has_md(self.h, 1 if tumor else 0))
+
+    # ---- device read selection: the loaded alignments as a table, the windows of a range as a slice (include/lancet_host.h).
+    #      Both structs point into arrays the host object owns: they are valid until the next call of the same method (and a reload).
+    def alignment_table(self, opts: LancetHostOpts, params) -> "abi.LancetAlignmentTable":
+        """What is loaded, for engine.DeviceReads: tumor then normal, filter bits for `opts`, reads packed for `params`' thresholds."""
+        t = abi.LancetAlignmentTable()
+        if self.L.lancet_host_alignment_table(self.h, C.byref(opts), C.byref(params), C.byref(t)) != 0:
+            raise engine.EngineError(self.L.lancet_host_last_error(self.h).decode())
+        t._keep = self
+        return t
+
+    def windows(self, w_begin: int, w_end: int, opts: LancetHostOpts) -> "abi.LancetWindowSlice":
+        """The windows of [w_begin, w_end) behind the host-side window filters, for Engine.upload_windows; does not advance the host."""
+        s = abi.LancetWindowSlice()
+        if self.L.lancet_host_windows(self.h, w_begin, w_end, C.byref(opts), C.byref(s)) != 0:
+            raise engine.EngineError(self.L.lancet_host_last_error(self.h).decode())
+        s._keep = self
+        return s
+
+    def windows_done(self, w_begin: int, w_end: int) -> None:
+        """The range went through Engine.upload_windows (taken): advance the host past it."""
+        if self.L.lancet_host_windows_done(self.h, w_begin, w_end) != 0:
+            raise engine.EngineError(self.L.lancet_host_last_error(self.h).decode())
+
+    def load_range(self, w_begin: int, w_end: int, opts: LancetHostOpts) -> None:
+        if self.L.lancet_host_load_range(self.h, w_begin, w_end, C.byref(opts)) != 0:
+            raise engine.EngineError(self.L.lancet_host_last_error(self.h).decode())
+
+    def window_info(self, w: int):
+        """(header, contig name, start, end) of tiled window w."""
+        s, e = C.c_int32(), C.c_int32()
+        self.L.lancet_host_window_span(self.h, w, C.byref(s), C.byref(e))
+        return self.L.lancet_host_window_hdr(self.h, w).decode(), self.chroms()[self.L.lancet_host_window_chrom(self.h, w)], s.value, e.value
 
     def batch(self, w_begin: int, w_end: int, opts: LancetHostOpts, pack_params=None):
         """Windows [w_begin, w_end) of the tiling -> (batch, tiled indices of the windows kept).  Arrays are copied out.
