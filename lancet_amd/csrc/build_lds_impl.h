@@ -461,6 +461,19 @@ struct CmpGraph {
   DEVM uint32_t color(uint32_t n) const { return col[n]; }
   DEVM void set_color(uint32_t n, uint32_t v) { col[n] = (uint8_t)v; }
 };
+// ... and its untouched lists as an edge view for the compression rules (kernels.h merge_link, adopted_edge, redirected_edge)
+struct BlcEdges {
+  LC_LDS const uint16_t *E; LC_LDS const uint8_t *NE, *FL;
+  DEVM bool special(uint32_t n) const { return (FL[n] & 12u) != 0; }
+  DEVM uint32_t e_to(uint32_t e) const { return BLC_TO(e); }
+  DEVM uint32_t e_dir(uint32_t e) const { return BLC_DIR(e); }
+  DEVM uint32_t e_make(uint32_t to, uint32_t dir, uint32_t) const { return BLC_MAKE(to, dir); }
+  template <class F> DEVM void for_each_edge(uint32_t n, F f) const {
+    const int cnt = (int)NE[n];
+#pragma unroll 1
+    for (int i = 0; i < cnt; ++i) f(i, (uint32_t)E[8 * n + (uint32_t)i]);
+  }
+};
 DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const EngineCaps *C, BL_S &S, BlScratch &X, LC_GLOBAL uint8_t *area, const int K_,
                              const uint32_t N_, const uint32_t nsurv_, const uint32_t ncand_, const int reflen_, const uint32_t ht_bc_, const uint32_t refmask_) {
   P = lc_sgpr(P); C = lc_sgpr(C); area = lc_sgpr(area);                        // (uniform arguments: scalar registers, wave.h lc_sgpr)
@@ -618,29 +631,12 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   };
   BLPA(S, 5);
   // ---- compress_prepare: the mergeable link of every node in either direction
-  auto buddy = [&](uint32_t u, char dir) -> int {                               // Node_t::getBuddy
-    if (FL[u] & 12u) return -1;
-    int ret = -1; const int cnt = (int)NE[u];
-    for (int i = 0; i < cnt; ++i) if (is_dir(BLC_DIR(E[8 * u + i]), dir)) { if (ret != -1) return -1; ret = i; }
-    if (ret != -1 && BLC_TO(E[8 * u + ret]) == u) return -1;
-    return ret;
-  };
-  auto tandem = [&](uint32_t u) -> bool { const int cnt = (int)NE[u]; for (int i = 0; i < cnt; ++i) if (BLC_TO(E[8 * u + i]) == u) return true; return false; };
+  BlcEdges ev; ev.E = E; ev.NE = NE; ev.FL = FL;
   WG_FOR(u, Pn) {
-    uint32_t l0 = 0, l1 = 0;
-    if (!(FL[u] & (12u | 32u)) && !tandem((uint32_t)u)) {
-      for (int sd = 0; sd < 2; ++sd) {
-        const int uid = buddy((uint32_t)u, sd == 0 ? 'F' : 'R');
-        if (uid < 0) continue;
-        const uint32_t ew = E[8 * (uint32_t)u + (uint32_t)uid], edir = BLC_DIR(ew), b = BLC_TO(ew);
-        if ((FL[b] & 12u) || tandem(b)) continue;
-        const int buid = buddy(b, (edir == 0 || edir == 2) ? 'R' : 'F');
-        if (buid < 0) continue;
-        if (BLC_TO(E[8 * b + (uint32_t)buid]) != (uint32_t)u) { S.why = 4; continue; }      // an irregular link: the literal replay's business
-        (sd == 0 ? l0 : l1) = CL_VALID | (edir << 28) | b;
-      }
-    }
-    LNK[2 * u] = l0; LNK[2 * u + 1] = l1;
+    uint32_t lF = 0, lR = 0;
+    if (!(FL[u] & 32u)) { lF = merge_link(ev, (uint32_t)u, 'F'); lR = merge_link(ev, (uint32_t)u, 'R'); }
+    if ((lF | lR) & CL_IRREG) S.why = 4;                                         // an irregular link: the literal replay's business
+    LNK[2 * u] = lF & CL_VALID ? lF : 0u; LNK[2 * u + 1] = lR & CL_VALID ? lR : 0u;
   }
   if (bl_bcast(&S.why)) return;
   BLPA(S, 6);
@@ -648,15 +644,10 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   WG_FOR(u, Pn) {
     for (uint32_t sd = 0; sd < 2; ++sd) {
       const uint32_t l = LNK[2 * u + sd];
-      lc_u4 r; r.x = LC_NIL; r.y = 0; r.z = (uint32_t)u; r.w = 2u * (uint32_t)u + sd;
-      if (l & CL_VALID) {
-        const uint32_t B = CL_TO(l), ed = CL_DIR(l);
-        const uint32_t sb = (ed == 0 || ed == 2) ? 1u : 0u;
-        const uint32_t back = LNK[2 * B + sb];
-        if (!(back & CL_VALID) || CL_TO(back) != (uint32_t)u || CL_DIR(back) != fliplink(ed)) S.why = 5;
-        r.x = 2u * B + (1u - sb); r.y = 1u | (((ed == 1 || ed == 2) ? 1u : 0u) << 31);
-      }
-      PT[2u * (uint32_t)u + sd] = pr_pack(r);
+      const uint32_t B = CL_TO(l), back = (l & CL_VALID) ? LNK[2 * B + link_side(CL_DIR(l))] : 0u;      // (nodes are their positions here)
+      bool irr = false;
+      PT[2u * (uint32_t)u + sd] = pr_pack(port_init(l, back, B, (uint32_t)u, (uint32_t)u, sd, &irr));
+      if (irr) S.why = 5;
     }
   }
   if (bl_bcast(&S.why)) return;
@@ -674,10 +665,7 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
       const int l = (int)threadIdx.x;
       for (int q = 0; q < 4; ++q) {
         const int p = l + q * BL_WG; have[q] = p < NP;
-        if (have[q]) { r[q] = pr_unpack(PT[p]); if (r[q].x != LC_NIL) { const lc_u4 t = pr_unpack(PT[r[q].x]);
-          r[q].y = (((r[q].y & 0x7FFFFFFFu) + (t.y & 0x7FFFFFFFu)) & 0x7FFFFFFFu) | ((r[q].y ^ t.y) & 0x80000000u);
-          if (t.z < r[q].z) r[q].z = t.z;
-          r[q].w = t.w; r[q].x = t.x; if (r[q].x != LC_NIL) chg = true; } }
+        if (have[q]) { r[q] = pr_unpack(PT[p]); if (r[q].x != LC_NIL) { r[q] = port_jump(r[q], pr_unpack(PT[r[q].x])); if (r[q].x != LC_NIL) chg = true; } }
       }
       __syncthreads();
       for (int q = 0; q < 4; ++q) if (have[q]) PT[l + q * BL_WG] = pr_pack(r[q]);
@@ -690,10 +678,7 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
         std::vector<unsigned long long> nxt((size_t)NP);
         for (int p = 0; p < NP; ++p) {
           lc_u4 a = pr_unpack(PT[p]);
-          if (a.x != LC_NIL) { const lc_u4 t = pr_unpack(PT[a.x]);
-            a.y = (((a.y & 0x7FFFFFFFu) + (t.y & 0x7FFFFFFFu)) & 0x7FFFFFFFu) | ((a.y ^ t.y) & 0x80000000u);
-            if (t.z < a.z) a.z = t.z;
-            a.w = t.w; a.x = t.x; if (a.x != LC_NIL) chg = true; }
+          if (a.x != LC_NIL) { a = port_jump(a, pr_unpack(PT[a.x])); if (a.x != LC_NIL) chg = true; }
           nxt[(size_t)p] = pr_pack(a);
         }
         for (int p = 0; p < NP; ++p) PT[p] = nxt[(size_t)p];
@@ -714,8 +699,8 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
     uint32_t hs = 0, al = 0;
     if ((uint32_t)u < Pn) {
       const lc_u4 a = pr_unpack(PT[2 * (size_t)u]), b = pr_unpack(PT[2 * (size_t)u + 1]);
-      const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu, cmin = a.z < b.z ? a.z : b.z;
-      if (mF + mR > 0 && cmin == (uint32_t)u) {
+      const uint32_t mF = port_cnt(a), mR = port_cnt(b);
+      if (port_is_head(a, b, (uint32_t)u)) {
         hs = mF + mR; al = (uint32_t)K + mF + mR;
         const uint32_t hx = dev_atomic_add((LC_LDS uint32_t *)&S.flagged, 1u);
         if (hx < PB_CHEADS) { HL[hx] = (uint16_t)u; HX[u] = (uint16_t)hx; HACC[4 * hx] = 0x7FFFFFFFu; HACC[4 * hx + 1] = 0x7FFFFFFFu; HACC[4 * hx + 2] = 0; HACC[4 * hx + 3] = 0; }
@@ -736,36 +721,25 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   // ---- every merged k-mer: its head, side, place in the merge order; descriptor into the head's deque, coverage into its slice
   WG_FOR(u, Pn) {
     const lc_u4 a = pr_unpack(PT[2 * (size_t)u]), b = pr_unpack(PT[2 * (size_t)u + 1]);
-    const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu;
-    if (mF + mR == 0) continue;
-    const uint32_t cmin = a.z < b.z ? a.z : b.z;
+    if (port_cnt(a) + port_cnt(b) == 0) continue;
+    const uint32_t cmin = port_cmin(a, b);
     if (cmin == (uint32_t)u) continue;                                         // a head
-    const uint32_t sH = (a.z == cmin) ? 0u : 1u;
-    const lc_u4 away = sH ? a : b;
-    const lc_u4 hF = pr_unpack(PT[2 * (size_t)cmin]), hR = pr_unpack(PT[2 * (size_t)cmin + 1]);
-    const bool onF = away.w == hF.w && (hF.y & 0x7FFFFFFFu) > 0;
-    const lc_u4 hp = onF ? hF : hR;
-    const uint32_t mdir = hp.y & 0x7FFFFFFFu, hmF = hF.y & 0x7FFFFFFFu, hmR = hR.y & 0x7FFFFFFFu;
-    const uint32_t j = mdir - (away.y & 0x7FFFFFFFu);
-    const uint32_t st_j = ((hp.y ^ away.y) >> 31) & 1u;
-    const uint32_t raw = fliplink(CL_DIR(LNK[2 * u + sH]));
-    const uint32_t st_p = st_j ^ ((raw == 1 || raw == 2) ? 1u : 0u);
-    const uint32_t edir = st_p ? flipme(raw) : raw;
-    const bool brev = (edir == 1 || edir == 3);
+    const PortPlace pp = port_place(a, b, pr_unpack(PT[2 * (size_t)cmin]), pr_unpack(PT[2 * (size_t)cmin + 1]), LNK[2 * u + port_head_side(a, b)]);
+    const uint32_t st_j = pp.st_j, edir = pp.edir; const bool brev = pp.brev;
     uint32_t ci; const unsigned long long kk = node_key((uint32_t)u, &ci);
     const uint32_t n = sidv[pos2si[u]];
     const uint32_t d0 = SD_MAKE(n, 0, key_base(&kk, K, 0)), dK = SD_MAKE(n, K - 1, key_base(&kk, K, K - 1));
     const uint32_t nb = AL[cmin];
-    const uint32_t d = brev ? (d0 ^ 3u) : dK;
-    if (onF) cseq[nb + hmR + (uint32_t)K + (j - 1u)] = d; else cseq[nb + hmR - j] = d ^ 3u;
-    const uint32_t t = HS[cmin] + (onF ? j - 1u : hmF + j - 1u);
+    const uint32_t d = kmer_end_desc(d0, dK, brev);
+    cseq[nb + port_deque_slot(pp, K)] = pp.onF ? d : d ^ 3u;
+    const uint32_t t = HS[cmin] + port_slice_slot(pp);
     const unsigned long long c4 = TCC[u];
     const uint32_t c0 = (uint32_t)(c4 & 0xFFFFu), c1 = (uint32_t)((c4 >> 16) & 0xFFFFu), c2 = (uint32_t)((c4 >> 32) & 0xFFFFu), c3 = (uint32_t)(c4 >> 48);
     ORD[t] = recov ? c4 + (unsigned long long)X.ord[pos2si[u]] : c4;         // (the merge operand is the float coverage: Tf, Tr are the two low fields; mincov below stays on the counts)
     LC_GLOBAL const uint16_t *q0p = qv + ((size_t)ci * K + 0) * 4, *qKp = qv + ((size_t)ci * K + (size_t)(K - 1)) * 4;
     const uint32_t tq0 = (uint32_t)q0p[0] + q0p[1] + q0p[2] + q0p[3], tqK = (uint32_t)qKp[0] + qKp[1] + qKp[2] + qKp[3];
     const uint32_t fl = FL[u] & 3u, hx = HX[cmin];
-    dev_atomic_min(&HACC[4 * hx], c0 + c1 + c2 + c3); dev_atomic_min(&HACC[4 * hx + 1], brev ? tq0 : tqK);
+    dev_atomic_min(&HACC[4 * hx], c0 + c1 + c2 + c3); dev_atomic_min(&HACC[4 * hx + 1], kmer_end_tq(tq0, tqK, brev));
     if (fl) dev_atomic_or(&HACC[4 * hx + 2], fl);
     if (fl == 1u) dev_atomic_add(&HACC[4 * hx + 3], 1u);
     HEADOF[u] = (uint16_t)cmin; INFO[u] = (uint8_t)(1u | (st_j << 1) | (edir << 2));
@@ -778,27 +752,24 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
   WG_FOR(hx, nheads) {
     const uint32_t u = HL[hx];
     const lc_u4 a = pr_unpack(PT[2 * (size_t)u]), b = pr_unpack(PT[2 * (size_t)u + 1]);
-    const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu;
+    const uint32_t mF = port_cnt(a), mR = port_cnt(b);
     uint32_t ci; const unsigned long long kk = node_key(u, &ci);
     const uint32_t si = pos2si[u], n = sidv[si];
     const uint32_t nb = AL[u];
     for (int t = 0; t < K; ++t) cseq[nb + mR + (uint32_t)t] = SD_MAKE(n, t, key_base(&kk, K, t));
     uint16_t el[13]; int m = 0; bool bad = false;
-    const int uF = mF ? buddy(u, 'F') : -1, uR = mR ? buddy(u, 'R') : -1;
+    const int uF = mF ? buddy_idx(ev, u, 'F') : -1, uR = mR ? buddy_idx(ev, u, 'R') : -1;
     if ((mF && uF < 0) || (mR && uR < 0)) bad = true;
     for (int e = 0; e < (int)NE[u]; ++e) { if (e == uF || e == uR) continue; el[m++] = E[8 * u + (uint32_t)e]; }
     for (int side = 0; side < 2 && !bad; ++side) {
       if (!(side == 0 ? mF : mR)) continue;
       const uint32_t En = ((side == 0 ? a.w : b.w) >> 1);                     // the end of the list in that direction
       const uint32_t info = INFO[En], ed = (info >> 2) & 3u, st = (info >> 1) & 1u;
-      const int buid = buddy(En, (ed == 0 || ed == 2) ? 'R' : 'F');
+      const int buid = buddy_idx(ev, En, link_bdir(ed));
       for (int e = 0; e < (int)NE[En]; ++e) {
         if (e == buid) continue;
-        const uint32_t be = E[8 * En + (uint32_t)e];
-        uint32_t ndir = BLC_DIR(be); if (st) ndir = flipme(ndir);
-        const uint32_t other = BLC_TO(be);
         if (m >= 12) { bad = true; break; }
-        el[m++] = BLC_MAKE(other == En ? u : other, ndir);
+        el[m++] = (uint16_t)adopted_edge(ev, E[8 * En + (uint32_t)e], st != 0, En, u);
       }
     }
     if (bad) { S.why = 6; continue; }
@@ -853,8 +824,8 @@ DEVNI void bl_compress_first(LC_GLOBAL const lancet_params *P, LC_GLOBAL const E
     }
     for (int e = 0; e < cnt; ++e) {
       uint32_t ew = head ? NEWE[13 * (size_t)hx + 1 + (size_t)e] : E[8 * (uint32_t)u + (uint32_t)e];
-      uint32_t to = BLC_TO(ew), dir = BLC_DIR(ew);
-      if (FL[to] & 16u) { dir ^= (INFO[to] >> 1) & 1u; to = HEADOF[to]; }
+      if (FL[BLC_TO(ew)] & 16u) ew = redirected_edge(ev, ew, HEADOF[BLC_TO(ew)], (INFO[BLC_TO(ew)] >> 1) & 1u);
+      const uint32_t to = BLC_TO(ew), dir = BLC_DIR(ew);
       G.edges[e] = ED_MAKE(to < nsurv ? sidv[pos2si[to]] : PB_SPECIAL + (to - nsurv), dir);
       if (head) NEWE[13 * (size_t)hx + 1 + (size_t)e] = BLC_MAKE(to, dir); else E[8 * (uint32_t)u + (uint32_t)e] = BLC_MAKE(to, dir);      // (the final list by position too: the cycle check below)
     }

@@ -859,20 +859,6 @@ DEV bool n_special(const Ctx &c, uint32_t n) { return (LC_CTX(c).W->gr[n].flags 
 DEV int n_len(const Ctx &c, uint32_t n) { return (int)(LC_CTX(c).W->gr[n].seq_hi - LC_CTX(c).W->gr[n].seq_lo); }   // str_m.length()
 DEV int n_strlen(const Ctx &c, uint32_t n) { return n_special(c, n) ? 0 : n_len(c, n); }       // Node_t::strlen
 
-DEV int get_buddy(const Ctx &c, uint32_t n, char dir) {             // Node_t::getBuddy, reference src/Node.cc:235-266
-  if (n_special(c, n)) return -1;
-  int ret = -1;
-  const uint32_t *e = LC_CTX(c).W->gr[n].edges;
-  int cnt = (int)LC_CTX(c).W->gr[n].necnt;
-  for (int i = 0; i < cnt; ++i) if (is_dir(ED_DIR(e[i]), dir)) { if (ret != -1) return -1; ret = i; }
-  if (ret != -1 && ED_TO(e[ret]) == n) return -1;
-  return ret;
-}
-DEV bool is_tandem(const Ctx &c, uint32_t n) {                      // reference src/Node.cc:123-134
-  const uint32_t *e = LC_CTX(c).W->gr[n].edges;
-  for (int i = 0; i < (int)LC_CTX(c).W->gr[n].necnt; ++i) if (ED_TO(e[i]) == n) return true;
-  return false;
-}
 DEV void add_edge(Ctx &c, uint32_t n, uint32_t to, uint32_t dir) {  // reference src/Node.cc:140-175
   uint32_t *e = LC_CTX(c).W->gr[n].edges;
   int cnt = (int)LC_CTX(c).W->gr[n].necnt;
@@ -2616,78 +2602,231 @@ DEVNI void clean_dead_wg(Ctx &c) {
   WG_LANE0 { S.M = (uint32_t)live; S.ht_elt -= (uint32_t)(M - live); evt(c, EV_CLEANDEAD, (uint32_t)(M - live)); }
 }
 
-DEV void recompute_after_append(Ctx &c, uint32_t n, uint32_t from, uint32_t to) {
-  // Node_t::computeMinCov over the merged arrays == min(old minima, minima over the appended descriptors)
-  LC_GLOBAL Work &W = *LC_CTX(c).W;
-  int mn = W.gr[n].mincov, mq = W.gr[n].mincovqv;
-  for (uint32_t i = from; i < to; ++i) { int t, tq; desc_tot(c, W.seq[i], &t, &tq); if (t < mn) mn = t; if (tq < mq) mq = tq; }
-  W.gr[n].mincov = mn; W.gr[n].mincovqv = mq;
+// ---------------------------------------------------------------------------------------------------------
+// The rules of Graph_t::compressNode (reference src/Graph.cc:2486-2706), each stated once for every driver of the compression: the
+// literal loop (compress_node), the record replay (compress_fast), pointer jumping over ports (compress_rank), the whole-wave loop
+// (compress_node_wv), the candidate test of compress_wg, and bl_compress_first of the build kernel (build_lds_impl.h).
+// Edges are read through a small view, as cycle_dfs reads graphs:
+//   special(n)                 n is the source or the sink
+//   e_to(e), e_dir(e)          neighbour and direction of an edge word;  e_make(to, dir, like): a word that keeps what else `like` carries
+//   for_each_edge(n, f)        f(i, e) for every edge of n, in list order
+// Three views: GrEdges (the node records in memory), GrLine0 (one node's record half in registers), BlcEdges (the build kernel's lists in LDS).
+// ---------------------------------------------------------------------------------------------------------
+#define CL_VALID 0x80000000u                                     /* a mergeable link: CL_VALID | edge dir << 28 | buddy                    */
+#define CL_IRREG 0x40000000u                                     /* ... whose buddy's edge does not come back (never together with CL_VALID) */
+#define CL_TO(l) ((l) & 0x0FFFFFFFu)
+#define CL_DIR(l) (((l) >> 28) & 3u)
+struct GrEdges {
+  LC_GLOBAL const NodeGr *gr;
+  DEVM bool special(uint32_t n) const { return (gr[n].flags & NF_SPECIAL) != 0; }
+  DEVM uint32_t e_to(uint32_t e) const { return ED_TO(e); }
+  DEVM uint32_t e_dir(uint32_t e) const { return ED_DIR(e); }
+  DEVM uint32_t e_make(uint32_t to, uint32_t dir, uint32_t like) const { return ED_MAKE(to, dir) | (like & (1u << 30)); }
+  template <class F> DEVM void for_each_edge(uint32_t n, F f) const { const int cnt = (int)gr[n].necnt; for (int i = 0; i < cnt; ++i) f(i, gr[n].edges[i]); }
+};
+DEV GrEdges gr_edges(const Ctx &c) { GrEdges v; v.gr = LC_CTX(c).W->gr; return v; }
+// First half of a node record (flags, degree, component, colour, the 12 edge words) in registers: the link tests of compress_prepare
+// look at a node's and its neighbours' edges a dozen times each; field by field that was ~100 dependent (L1-hit) loads per node.
+// The loops run over all 12 slots with a predicate, so that the edge words stay in registers (an array indexed at run time would
+// live in scratch memory).  As a view it holds the one node it was loaded from.
+#define LC_L0_EACH(g, X) do { X(0, (g).e0); X(1, (g).e1); X(2, (g).e2); X(3, (g).e3); X(4, (g).e4); X(5, (g).e5); X(6, (g).e6); X(7, (g).e7); X(8, (g).e8); X(9, (g).e9); X(10, (g).e10); X(11, (g).e11); } while (0)
+struct GrLine0 {
+  uint32_t flags, necnt; int comp; uint32_t color; uint32_t e0, e1, e2, e3, e4, e5, e6, e7, e8, e9, e10, e11;
+  DEVM bool special(uint32_t) const { return (flags & NF_SPECIAL) != 0; }
+  DEVM uint32_t e_to(uint32_t e) const { return ED_TO(e); }
+  DEVM uint32_t e_dir(uint32_t e) const { return ED_DIR(e); }
+  DEVM uint32_t e_make(uint32_t to, uint32_t dir, uint32_t like) const { return ED_MAKE(to, dir) | (like & (1u << 30)); }
+  template <class F> DEVM void for_each_edge(uint32_t, F f) const {
+#define LC_X(i, e) do { if ((uint32_t)(i) < necnt) f((i), (e)); } while (0)
+    LC_L0_EACH(*this, LC_X);
+#undef LC_X
+  }
+};
+DEV GrLine0 gr_line0(LC_GLOBAL const NodeGr *g) {
+  LC_GLOBAL const uint32_t *p = (LC_GLOBAL const uint32_t *)g;
+  const lc_u4 a = ldg4(p), b = ldg4(p + 4), c = ldg4(p + 8), d = ldg4(p + 12);
+  GrLine0 r; r.flags = a.x; r.necnt = a.y; r.comp = (int)a.z; r.color = a.w;
+  r.e0 = b.x; r.e1 = b.y; r.e2 = b.z; r.e3 = b.w; r.e4 = c.x; r.e5 = c.y; r.e6 = c.z; r.e7 = c.w; r.e8 = d.x; r.e9 = d.y; r.e10 = d.z; r.e11 = d.w;
+  return r;
 }
+// ---- the mergeable link
+// Node_t::getBuddy (reference src/Node.cc:235-266): index of the one edge of n in direction dir and its word, or -1 (none, several,
+// an edge to n itself, n a special node)
+template <class V> DEV int buddy_idx(const V &v, uint32_t n, char dir, uint32_t *ew_out = nullptr) {
+  if (v.special(n)) return -1;
+  int ret = -1, cnt = 0; uint32_t ew = 0;
+  v.for_each_edge(n, [&](int i, uint32_t e) { if (is_dir(v.e_dir(e), dir)) { ret = i; ew = e; ++cnt; } });
+  if (cnt != 1 || v.e_to(ew) == n) return -1;
+  if (ew_out) *ew_out = ew;
+  return ret;
+}
+template <class V> DEV bool tandem(const V &v, uint32_t n) {      // Node_t::isTandem (reference src/Node.cc:123-134): an edge to itself
+  bool t = false;
+  v.for_each_edge(n, [&](int, uint32_t e) { if (v.e_to(e) == n) t = true; });
+  return t;
+}
+DEV uint32_t link_side(uint32_t edir) { return (edir == 0 || edir == 2) ? 1u : 0u; }      // the side of the buddy a link arrives at: 0 its F, 1 its R side
+DEV char link_bdir(uint32_t edir) { return link_side(edir) ? 'R' : 'F'; }                 // ... as the direction its buddy edge must have (compressNode's bdir)
+DEV bool link_flips(uint32_t edir) { return edir == 1 || edir == 2; }                     // FR / RF: the buddy's frame is the head's, flipped (flipme on what it brings)
+// compressNode's test of node n in direction dir, in two halves because the record of the buddy may have to be fetched in between.
+// n's own half: n is no tandem and has a buddy -> CL_VALID | edge dir << 28 | buddy (*uid: where the edge stands in n's list), else 0.
+template <class V> DEV uint32_t link_out(const V &v, uint32_t n, char dir, int *uid = nullptr) {
+  uint32_t ew = 0;
+  const int i = buddy_idx(v, n, dir, &ew);
+  if (i < 0 || tandem(v, n)) return 0;
+  if (uid) *uid = i;
+  return CL_VALID | (v.e_dir(ew) << 28) | v.e_to(ew);
+}
+// The buddy's half (vb holds the buddy): it is no tandem and has a buddy itself in bdir -> l (*buid: where that edge stands), else 0.
+// The reference does not look where that edge leads; in a graph whose edges all have their twins it leads back to n.  Where it does
+// not, the link comes back as CL_IRREG | dir << 28 | buddy: the literal loop merges it like any other, the other drivers step aside.
+template <class VB> DEV uint32_t link_back(const VB &vb, uint32_t n, uint32_t l, int *buid = nullptr) {
+  if (!(l & CL_VALID)) return 0;
+  const uint32_t b = CL_TO(l); uint32_t bew = 0;
+  if (tandem(vb, b)) return 0;
+  const int i = buddy_idx(vb, b, link_bdir(CL_DIR(l)), &bew);
+  if (i < 0) return 0;
+  if (buid) *buid = i;
+  return vb.e_to(bew) == n ? l : ((l & ~CL_VALID) | CL_IRREG);
+}
+template <class V> DEV uint32_t merge_link(const V &v, uint32_t n, char dir, int *uid = nullptr, int *buid = nullptr) {      // (one view holds both nodes)
+  return link_back(v, n, link_out(v, n, dir, uid), buid);
+}
+DEV int get_buddy(const Ctx &c, uint32_t n, char dir) { return buddy_idx(gr_edges(c), n, dir); }
+// ---- edge adoption: the outward edges of the absorbed end `end` become edges of the head
+// the word the head gets for edge `be` of the end: its direction flipped when the end's frame is (flipme), an edge of the end to itself
+// becomes one of the head to itself, what else the word carries (bit 30) is kept
+template <class V> DEV uint32_t adopted_edge(const V &v, uint32_t be, bool flip, uint32_t end, uint32_t head) {
+  const uint32_t to = v.e_to(be), d = v.e_dir(be);
+  return v.e_make(to == end ? head : to, flip ? flipme(d) : d, be);
+}
+// an edge `ew` into an absorbed node goes to its head instead; it arrives the other way round when the absorbed node's frame was
+// flipped against the head's (Node_t::updateEdge keeps its place and bit 30)
+template <class V> DEV uint32_t redirected_edge(const V &v, uint32_t ew, uint32_t head, uint32_t flipped) { return v.e_make(head, v.e_dir(ew) ^ flipped, ew); }
+// The serial form (reference src/Graph.cc:2674-2704): every edge of `buddy` (read through vb) but the one at buid, in list order, is
+// pushed back on the head's list and its twin at the far node updated in place.  false: the head's list is full (overflow flagged).
+template <class VB> DEV bool adopt_edges(Ctx &c, const VB &vb, uint32_t head, uint32_t buddy, int buid, uint32_t edir) {
+  LC_GLOBAL NodeGr &H = LC_CTX(c).W->gr[head];
+  const GrEdges hv = gr_edges(c);
+  bool ok = true;
+  vb.for_each_edge(buddy, [&](int i, uint32_t be) {
+    if (!ok || i == buid) return;
+    const int cnt = (int)H.necnt;
+    if (cnt >= LC_EMAX) { OVF(c); ok = false; return; }
+    const uint32_t ne = adopted_edge(hv, be, link_flips(edir), buddy, head);
+    H.edges[cnt] = ne; H.necnt = (uint32_t)(cnt + 1);
+    if (ED_TO(be) != buddy) update_edge(c, ED_TO(be), buddy, fliplink(ED_DIR(be)), head, fliplink(ED_DIR(ne)));
+  });
+  return ok;
+}
+// ---- the coverage of a merged node (reference src/Graph.cc:2632-2636), the reference's expression in its order: nc over amer k-mers
+// takes in bc over bmer.  The tests compare coverages bit for bit (-ffp-contract=off).
+template <class T> DEV float merge_cov(float nc, T amer, float bc, T bmer) { return ((nc * amer) + (bc * bmer)) / (amer + bmer); }
+// The same value for one more k-mer (bmer = 1) with the division by the integer amer + 1 done as (float)((double)numerator * rcp),
+// rcp = 1.0 / (double)(amer + 1): that IS the correctly rounded float quotient -- the double product is off by less than 2^-52 relative
+// (two roundings of 2^-53), while the exact quotient of two 24-bit floats is either a float or more than 2^-49 relative away from every
+// midpoint between two floats (|A * 2^24 - M * B| >= 1 for an odd M: B < 2^24 cannot divide it out), so rounding the product to float
+// rounds as the quotient does (no overflow / subnormals: coverages below 65 536, divisors below 4097).  Five dependent instructions
+// per merge instead of the IEEE division's twelve.
+DEV float merge_cov_rcp(float nc, int amer, float bc, double rcp) { const int bmer = 1; const float num = (nc * amer) + (bc * bmer); return (float)((double)num * rcp); }
+// ---- what a one-k-mer node brings to the unitig it is merged into: the descriptor of its last base, or of its first one complemented
+// when it is entered against its own direction (brev = dir_dest(edir) == 'R'), and that position's quality total
+DEV bool link_brev(uint32_t edir) { return dir_dest(edir) == 'R'; }
+DEV uint32_t kmer_end_desc(uint32_t d0, uint32_t dK, bool brev) { return brev ? (d0 ^ 3u) : dK; }
+template <class T> DEV T kmer_end_tq(T tq0, T tqK, bool brev) { return brev ? tq0 : tqK; }
 
-DEVNI void compress_node(Ctx &c, uint32_t node, char dir) {          // Graph_t::compressNode, reference src/Graph.cc:2486-2706
+// ---- Graph_t::compressNode itself (reference src/Graph.cc:2486-2706): node takes in its buddy in direction dir for as long as it has a
+// mergeable link there.  The node-level logic is written once; what differs is who runs the loops over descriptors -- the copy of the
+// absorbed node's descriptors, Node_t::computeMinCov over them (== min(old minima, minima behind the appended descriptors)), the move of
+// a deque that has no room left (seq_reserve's decision):
+//   WV = false  the calling lane alone, plain loops (compress_node: compress, the ring fallback of compress_fast, and compress_wg of the
+//               re-run tier, whose helper waves must not run ahead of wave 0 through code without barriers);
+//   WV = true   the whole wave of the single-wave window kernel (compress_node_wv).  The passes that follow the first compress join unitigs
+//               of a hundred k-mers and more: a load, a store and three dependent loads per descriptor, on one lane ~100 us of the ~120 us
+//               removeTips took per window.  Every lane runs the node-level logic on the same values (uniform loads of the two records;
+//               only lane 0 stores), the descriptor loops are shared out over the lanes.
+// Same merges in the same order, same float operations per merge.
+template <bool WV, class F> DEV void cn_each(uint32_t n, F f) {
+  if constexpr (WV) { WG_FOR(i, n) { f((uint32_t)i); } } else { for (uint32_t i = 0; i < n; ++i) f(i); }
+}
+template <bool WV> DEV void compress_node_t(Ctx &c, uint32_t node, char dir) {
   LC_GLOBAL Work &W = *LC_CTX(c).W; LC_WS &S = LC_SREF(c);
-  const int K = S.K;
-  while (!S.overflow) {
-    int uid = get_buddy(c, node, dir);
-    if (uid == -1) return;
-    if (is_tandem(c, node)) return;
-    uint32_t ew = W.gr[node].edges[uid];
-    uint32_t edir = ED_DIR(ew);
-    char bdir = (edir == 0 || edir == 2) ? 'R' : 'F';
-    uint32_t buddy = ED_TO(ew);
-    if (is_tandem(c, buddy)) return;
-    int buid = get_buddy(c, buddy, bdir);
-    if (buid == -1) return;
-    bool brev = dir_dest(edir) == 'R';
-    int alen = n_len(c, node), blen = n_len(c, buddy);
-    uint32_t tail = (uint32_t)(blen - (K - 1));
-    // merged = astr + bstr[K-1:]  (dir F: append ; dir R: prepend the reverse complement)
-    if (dir == 'F') {
-      if (!seq_reserve(c, node, 0, tail)) return;
-      uint32_t hi = W.gr[node].seq_hi, blo = W.gr[buddy].seq_lo, bhi = W.gr[buddy].seq_hi;
-      for (uint32_t t = 0; t < tail; ++t) {
-        uint32_t d = brev ? W.seq[bhi - 1 - ((uint32_t)(K - 1) + t)] : W.seq[blo + (uint32_t)(K - 1) + t];
-        if (brev) d ^= 3u;
-        W.seq[hi + t] = d;
+  auto U = [](uint32_t x) -> uint32_t { return WV ? (uint32_t)wg_uniform((int)x) : x; };
+  const int K = (int)U((uint32_t)S.K);
+#ifndef LANCET_WAVE_EMU
+  const bool l0 = WV ? wg_is_lane0() : true;
+#else
+  const bool l0 = true;
+#endif
+  while (!U((uint32_t)S.overflow)) {
+    LC_GLOBAL NodeGr *gn = &W.gr[node];
+    const GrLine0 G = gr_line0(gn);
+    int uid = -1, buid = -1;
+    const uint32_t lo_ = U(link_out(G, node, dir, &uid));
+    if (!lo_) return;
+    uid = (int)U((uint32_t)uid);
+    const uint32_t edir = CL_DIR(lo_), buddy = CL_TO(lo_);
+    LC_GLOBAL NodeGr *gb = &W.gr[buddy];
+    const GrLine0 B = gr_line0(gb);
+    if (!U(link_back(B, node, lo_, &buid))) return;                  // (an irregular link merges like any other: the reference does not look)
+    buid = (int)U((uint32_t)buid);
+    const bool brev = link_brev(edir);
+    // second halves of the two records: cov[4] | mincov mincovqv seq_lo seq_hi | seq_clo seq_chi nkm nkmT
+    const lc_u4 nc4 = ldg4((LC_GLOBAL const uint32_t *)gn + 16), nm4 = ldg4((LC_GLOBAL const uint32_t *)gn + 20), ns4 = ldg4((LC_GLOBAL const uint32_t *)gn + 24);
+    const lc_u4 bc4 = ldg4((LC_GLOBAL const uint32_t *)gb + 16), bm4 = ldg4((LC_GLOBAL const uint32_t *)gb + 20), bs4 = ldg4((LC_GLOBAL const uint32_t *)gb + 24);
+    uint32_t lo = U(nm4.z), hi = U(nm4.w), clo = U(ns4.x), chi = U(ns4.y);
+    const uint32_t blo = U(bm4.z), bhi = U(bm4.w);
+    const int alen = (int)(hi - lo), blen = (int)(bhi - blo);
+    const uint32_t tail = (uint32_t)(blen - (K - 1));
+    // seq_reserve: room for `tail` more descriptors behind (dir F) / in front (dir R); else the deque moves to the top of the arena
+    {
+      const uint32_t front = dir == 'F' ? 0u : tail, back = dir == 'F' ? tail : 0u;
+      if (!(lo - clo >= front && chi - hi >= back)) {
+        const uint32_t len = hi - lo, cap = 2 * (len + front + back) + 16;
+        const uint32_t top = U(S.seq_top);
+        if (top + cap > LC_CTX(c).C->seq_cap) { if (l0) OVF(c); return; }
+        const uint32_t nlo = top + (cap - len - front - back) / 2 + front;
+        cn_each<WV>(len, [&](uint32_t i) { W.seq[nlo + i] = W.seq[lo + i]; });
+        if (l0) { S.seq_top = top + cap; gn->seq_clo = top; gn->seq_chi = top + cap; }
+        clo = top; chi = top + cap; lo = nlo; hi = nlo + len;
       }
-      W.gr[node].seq_hi = hi + tail;
-      recompute_after_append(c, node, hi, hi + tail);
-    } else {
-      if (!seq_reserve(c, node, tail, 0)) return;
-      uint32_t lo = W.gr[node].seq_lo, blo = W.gr[buddy].seq_lo, bhi = W.gr[buddy].seq_hi;
-      // element t of B'[K-1:] lands at lo-1-t, complemented
-      for (uint32_t t = 0; t < tail; ++t) {
-        uint32_t d = brev ? W.seq[bhi - 1 - ((uint32_t)(K - 1) + t)] : W.seq[blo + (uint32_t)(K - 1) + t];
-        if (brev) d ^= 3u;
-        W.seq[lo - 1 - t] = d ^ 3u;
-      }
-      W.gr[node].seq_lo = lo - tail;
-      recompute_after_append(c, node, lo - tail, lo);
     }
-    W.gr[node].nkm += W.gr[buddy].nkm; W.gr[node].nkmT += W.gr[buddy].nkmT;
-    int amer = alen - K + 1, bmer = blen - K + 1;
-    float *nc = W.gr[node].cov; const float *bc = W.gr[buddy].cov;
-    for (int q = 0; q < 4; ++q) nc[q] = ((nc[q] * amer) + (bc[q] * bmer)) / (amer + bmer);      // Graph.cc:2632-2636
-    W.gr[buddy].flags |= NF_DEAD;
-    W.gr[node].flags |= (W.gr[buddy].flags & (NF_TUMOR | NF_NORMAL));
-    erase_edge_at(c, node, uid);
-    int bcnt = (int)W.gr[buddy].necnt;
-    for (int i = 0; i < bcnt; ++i) {
-      if (i == buid) continue;
-      uint32_t be = W.gr[buddy].edges[i];
-      uint32_t ndir = ED_DIR(be);
-      if (edir == 1 || edir == 2) ndir = flipme(ndir);
-      uint32_t other = ED_TO(be);
-      int cnt = (int)W.gr[node].necnt;
-      if (cnt >= LC_EMAX) { OVF(c); return; }
-      if (other == buddy) { W.gr[node].edges[cnt] = ED_MAKE(node, ndir) | (be & (1u << 30)); W.gr[node].necnt = cnt + 1; }
-      else {
-        W.gr[node].edges[cnt] = ED_MAKE(other, ndir) | (be & (1u << 30)); W.gr[node].necnt = cnt + 1;
-        update_edge(c, other, buddy, fliplink(ED_DIR(be)), node, fliplink(ndir));
-      }
+    // merged = astr + bstr[K-1:]  (dir F: append ; dir R: prepend the reverse complement), and the minima behind what is appended
+    if (WV && l0) { S.cn_mn = nm4.x; S.cn_mq = nm4.y; }
+    uint32_t mn = 0x7FFFFFFFu, mq = 0x7FFFFFFFu;
+    cn_each<WV>(tail, [&](uint32_t t) {
+      uint32_t d = brev ? W.seq[bhi - 1 - ((uint32_t)(K - 1) + t)] : W.seq[blo + (uint32_t)(K - 1) + t];
+      if (brev) d ^= 3u;
+      if (dir == 'F') W.seq[hi + t] = d; else { d ^= 3u; W.seq[lo - 1 - t] = d; }
+      int tt, tq; desc_tot(c, d, &tt, &tq);
+      if ((uint32_t)tt < mn) mn = (uint32_t)tt;
+      if ((uint32_t)tq < mq) mq = (uint32_t)tq;
+    });
+    uint32_t nmn, nmq;
+    if constexpr (WV) {
+      WG_FOR(l, LANCET_WG) { if (mn != 0x7FFFFFFFu) { dev_atomic_min((LC_LDS uint32_t *)&S.cn_mn, mn); dev_atomic_min((LC_LDS uint32_t *)&S.cn_mq, mq); mn = 0x7FFFFFFFu; } }
+      nmn = U(S.cn_mn); nmq = U(S.cn_mq);
+    } else { nmn = mn < nm4.x ? mn : nm4.x; nmq = mq < nm4.y ? mq : nm4.y; }
+    const int amer = alen - K + 1, bmer = blen - K + 1;
+    if (l0) {
+      if (dir == 'F') gn->seq_hi = hi + tail; else gn->seq_lo = lo - tail;
+      if (dir == 'F') { if (lo != nm4.z) gn->seq_lo = lo; } else { if (hi != nm4.w) gn->seq_hi = hi; }      // (the deque moved)
+      gn->mincov = (int)nmn; gn->mincovqv = (int)nmq;
+      gn->nkm = ns4.z + bs4.z; gn->nkmT = ns4.w + bs4.w;
+      const float ncv[4] = {__builtin_bit_cast(float, nc4.x), __builtin_bit_cast(float, nc4.y), __builtin_bit_cast(float, nc4.z), __builtin_bit_cast(float, nc4.w)};
+      const float bcv[4] = {__builtin_bit_cast(float, bc4.x), __builtin_bit_cast(float, bc4.y), __builtin_bit_cast(float, bc4.z), __builtin_bit_cast(float, bc4.w)};
+      for (int q = 0; q < 4; ++q) gn->cov[q] = merge_cov(ncv[q], amer, bcv[q], bmer);
+      gb->flags = B.flags | NF_DEAD;
+      gn->flags = G.flags | (B.flags & (NF_TUMOR | NF_NORMAL));
+      erase_edge_at(c, node, uid);
+      adopt_edges(c, gr_edges(c), node, buddy, buid, edir);           // (a full list: the overflow flag ends the loop)
     }
   }
 }
+DEVNI void compress_node(Ctx &c, uint32_t node, char dir) { compress_node_t<false>(c, node, dir); }
+#ifndef LANCET_FAT
+DEVNI void compress_node_wv(Ctx &c, uint32_t node, char dir) { compress_node_t<true>(c, node, dir); }
+#endif
 // ---------------------------------------------------------------------------------------------------------
 // First compress of a component (every node still is one k-mer): the same merges in the same order as
 // compress()/compress_node() above, but each merge costs ONE dependent memory access instead of a dozen.
@@ -2699,39 +2838,6 @@ DEVNI void compress_node(Ctx &c, uint32_t node, char dir) {          // Graph_t:
 //     descriptors, float averages in merge order, minima, flags; the last absorbed node's outward edges are
 //     attached exactly like compress_node does.
 // ---------------------------------------------------------------------------------------------------------
-#define CL_VALID 0x80000000u
-#define CL_TO(l) ((l) & 0x0FFFFFFFu)
-#define CL_DIR(l) (((l) >> 28) & 3u)
-// First half of a node record (flags, degree, component, colour, the 12 edge words) in registers: the link tests of compress_prepare
-// look at a node's and its neighbours' edges a dozen times each; field by field that was ~100 dependent (L1-hit) loads per node.
-// The loops run over all 12 slots with a predicate, so that the edge words stay in registers (an array indexed at run time would
-// live in scratch memory).
-struct GrLine0 { uint32_t flags, necnt; int comp; uint32_t color; uint32_t e0, e1, e2, e3, e4, e5, e6, e7, e8, e9, e10, e11; };
-DEV GrLine0 gr_line0(LC_GLOBAL const NodeGr *g) {
-  LC_GLOBAL const uint32_t *p = (LC_GLOBAL const uint32_t *)g;
-  const lc_u4 a = ldg4(p), b = ldg4(p + 4), c = ldg4(p + 8), d = ldg4(p + 12);
-  GrLine0 r; r.flags = a.x; r.necnt = a.y; r.comp = (int)a.z; r.color = a.w;
-  r.e0 = b.x; r.e1 = b.y; r.e2 = b.z; r.e3 = b.w; r.e4 = c.x; r.e5 = c.y; r.e6 = c.z; r.e7 = c.w; r.e8 = d.x; r.e9 = d.y; r.e10 = d.z; r.e11 = d.w;
-  return r;
-}
-#define LC_L0_EACH(g, X) do { X(0, (g).e0); X(1, (g).e1); X(2, (g).e2); X(3, (g).e3); X(4, (g).e4); X(5, (g).e5); X(6, (g).e6); X(7, (g).e7); X(8, (g).e8); X(9, (g).e9); X(10, (g).e10); X(11, (g).e11); } while (0)
-// Node_t::getBuddy on the registers: the one edge in direction dir (LC_NIL: none, several, a special node, or a self loop)
-DEV uint32_t l0_buddy(const GrLine0 &g, uint32_t self, char dir) {
-  if (g.flags & NF_SPECIAL) return LC_NIL;
-  uint32_t ew = LC_NIL; int cnt = 0;
-#define LC_X(i, e) do { if ((uint32_t)(i) < g.necnt && is_dir(ED_DIR(e), dir)) { ew = (e); ++cnt; } } while (0)
-  LC_L0_EACH(g, LC_X);
-#undef LC_X
-  if (cnt != 1 || ED_TO(ew) == self) return LC_NIL;
-  return ew;
-}
-DEV bool l0_tandem(const GrLine0 &g, uint32_t self) {
-  bool t = false;
-#define LC_X(i, e) do { if ((uint32_t)(i) < g.necnt && ED_TO(e) == self) t = true; } while (0)
-  LC_L0_EACH(g, LC_X);
-#undef LC_X
-  return t;
-}
 // descriptor i of candidate ci's k-mer while the descriptors are not materialised (load_prebuilt)
 DEV uint32_t seq_desc_lazy(const LC_WS &S, uint32_t node, uint32_t ci, int K, int i) {
   return SD_MAKE(node, i, pre_key_base((LC_GLOBAL const unsigned long long *)(uintptr_t)S.lz_skey, S.lz_kw, ci, K, i));
@@ -2767,36 +2873,22 @@ DEVNI void compress_prepare(Ctx &c, int comp) {
     const GrLine0 G = gr_line0(&gr[n]);
     LC_GLOBAL const uint32_t *g1 = (LC_GLOBAL const uint32_t *)&gr[n] + 16;
     const lc_u4 h0 = ldg4(g1), h1 = ldg4(g1 + 4), h2 = ldg4(g1 + 8), h3 = ldg4(g1 + 12);      // cov[4] | mincov mincovqv seq_lo seq_hi | seq_clo seq_chi nkm nkmT | nqv onref kc[4]
-    lc_u4 z; z.x = 0; z.y = 0; z.z = 0; z.w = 0;
-    todo[n] = 0;                                                 // "absorbed" mark of compress_fast / compress_rank (todo[] is idle after the build)
+    todo[n] = 0;                                                // "absorbed" mark of compress_fast / compress_rank (todo[] is idle after the build)
     if (G.comp != comp || (G.flags & (NF_DEAD | NF_SPECIAL))) { cmp[n].lnk[0] = 0; cmp[n].lnk[1] = 0; continue; }
     const uint32_t seq_lo = h1.z, seq_hi = h1.w, nkm = h2.z, nkmT = h2.w, nqv = h3.x;
     if ((int)(seq_hi - seq_lo) != K || nkm != 1 || nqv == LC_NIL) { cmp[n].lnk[0] = 0; cmp[n].lnk[1] = 0; S.cmp_ok = 0; continue; }
-    const bool tand = l0_tandem(G, n);
-    const uint32_t ewF = tand ? LC_NIL : l0_buddy(G, n, 'F'), ewR = tand ? LC_NIL : l0_buddy(G, n, 'R');
+    const uint32_t loF = link_out(G, n, 'F'), loR = link_out(G, n, 'R');
     // round trip 2: the two neighbours' records, the first / last descriptor, their per-position quality counts
-    const uint32_t bF = ewF != LC_NIL ? ED_TO(ewF) : n, bR = ewR != LC_NIL ? ED_TO(ewR) : n;
-    const GrLine0 BF = gr_line0(&gr[bF]), BR = gr_line0(&gr[bR]);
+    const GrLine0 BF = gr_line0(&gr[loF ? CL_TO(loF) : n]), BR = gr_line0(&gr[loR ? CL_TO(loR) : n]);
     uint32_t d0, dK;
     if (lazy && seq_lo == nqv * (uint32_t)K) {                  // (a k-mer node of a graph from the LDS build kernel: its descriptors follow from its key)
       d0 = seq_desc_lazy(S, n, nqv, K, 0); dK = seq_desc_lazy(S, n, nqv, K, K - 1);
     } else { d0 = seq[seq_lo]; dK = seq[seq_lo + (uint32_t)(K - 1)]; }
     LC_GLOBAL const uint16_t *q0p = qv + ((size_t)nqv * K + 0) * QS, *qKp = qv + ((size_t)nqv * K + (size_t)(K - 1)) * QS;
     const int tq0 = (int)q0p[0] + (int)q0p[1] + (int)q0p[2] + (int)q0p[3], tqK = (int)qKp[0] + (int)qKp[1] + (int)qKp[2] + (int)qKp[3];
-    bool irr = false;
-    uint32_t lnk[2] = {0u, 0u};
-    for (int sd = 0; sd < 2; ++sd) {
-      const uint32_t ew = sd == 0 ? ewF : ewR;
-      if (ew == LC_NIL) continue;
-      const uint32_t edir = ED_DIR(ew), bn = ED_TO(ew);
-      const GrLine0 &Bq = sd == 0 ? BF : BR;
-      if (l0_tandem(Bq, bn)) continue;
-      const char bdir = (edir == 0 || edir == 2) ? 'R' : 'F';
-      const uint32_t bew = l0_buddy(Bq, bn, bdir);
-      if (bew == LC_NIL) continue;
-      if (ED_TO(bew) != n) { irr = true; continue; }
-      lnk[sd] = CL_VALID | (edir << 28) | bn;
-    }
+    const uint32_t lF = link_back(BF, n, loF), lR = link_back(BR, n, loR);
+    const bool irr = ((lF | lR) & CL_IRREG) != 0;                // (an irregular link is none here: the literal loop's business)
+    const uint32_t lnk[2] = {lF & CL_VALID ? lF : 0u, lR & CL_VALID ? lR : 0u};
     // (the descriptors of a single k-mer node belong to the node itself: desc_tot's `tot` is the sum of its own four counts)
     const int tot = (int)(h3.z & 0xFFFFu) + (int)(h3.z >> 16) + (int)(h3.w & 0xFFFFu) + (int)(h3.w >> 16);
     lc_u4 r0, r1, r2;
@@ -2805,7 +2897,6 @@ DEVNI void compress_prepare(Ctx &c, int comp) {
     r2.x = d0; r2.y = dK; r2.z = (uint32_t)tot; r2.w = (uint32_t)tq0;                // d0 dK tot tq0
     LC_GLOBAL uint32_t *rp = (LC_GLOBAL uint32_t *)&cmp[n];
     stg4(rp, r0); stg4(rp + 4, r1); stg4(rp + 8, r2); rp[12] = (uint32_t)tqK;
-    (void)z; (void)h2;
     if (irr) S.cmp_ok = 0;
   }
   WG_SYNC();
@@ -2849,10 +2940,9 @@ DEVNI uint32_t compress_fast(Ctx &c, int comp, bool quiet = false) {
         if (B == H || cnt >= lcap) { ring = true; break; }
         LC_GLOBAL const CmpRec &rb = W.cmp[B];                               // the one dependent access of this merge
         list[2 * cnt] = B; list[2 * cnt + 1] = edir; ++cnt;
-        const char bdir = (edir == 0 || edir == 2) ? 'R' : 'F';
-        const uint32_t on = rb.lnk[bdir == 'R' ? 0 : 1];          // the absorbed node's link away from the head
+        const uint32_t on = rb.lnk[1u - link_side(edir)];         // the absorbed node's link away from the head
         valid = (on & CL_VALID) != 0;
-        if (valid) { uint32_t nd = CL_DIR(on); if (edir == 1 || edir == 2) nd = flipme(nd); edir = nd; B = CL_TO(on); }
+        if (valid) { uint32_t nd = CL_DIR(on); if (link_flips(edir)) nd = flipme(nd); edir = nd; B = CL_TO(on); }
       }
       if (ring) { ringed = true; compress_node(c, H, dir); continue; }           // untouched so far: the literal replay handles it
       if (cnt == 0) continue;
@@ -2877,16 +2967,14 @@ DEVNI uint32_t compress_fast(Ctx &c, int comp, bool quiet = false) {
         const uint32_t Bj = Bn, ed = en;
         const CmpRec rb = rn;
         if (j + 1 < cnt) { Bn = list[2 * j + 2]; en = list[2 * j + 3]; rn = W.cmp[Bn]; }
-        const bool brev = dir_dest(ed) == 'R';
-        uint32_t d = brev ? (rb.d0 ^ 3u) : rb.dK;
+        const bool brev = link_brev(ed);
+        const uint32_t d = kmer_end_desc(rb.d0, rb.dK, brev);
         if (dir == 'F') W.seq[hi++] = d; else W.seq[--lo] = d ^ 3u;
         if (rb.tot < mn) mn = rb.tot;
-        { const int tq = brev ? rb.tq0 : rb.tqK; if (tq < mq) mq = tq; }
-        const int amer = alen - K + 1, bmer = 1;                  // Graph.cc:2632-2636, same expression, same order
-        nc0 = ((nc0 * amer) + (rb.cov[0] * bmer)) / (amer + bmer);
-        nc1 = ((nc1 * amer) + (rb.cov[1] * bmer)) / (amer + bmer);
-        nc2 = ((nc2 * amer) + (rb.cov[2] * bmer)) / (amer + bmer);
-        nc3 = ((nc3 * amer) + (rb.cov[3] * bmer)) / (amer + bmer);
+        { const int tq = kmer_end_tq(rb.tq0, rb.tqK, brev); if (tq < mq) mq = tq; }
+        const int amer = alen - K + 1, bmer = 1;
+        nc0 = merge_cov(nc0, amer, rb.cov[0], bmer); nc1 = merge_cov(nc1, amer, rb.cov[1], bmer);
+        nc2 = merge_cov(nc2, amer, rb.cov[2], bmer); nc3 = merge_cov(nc3, amer, rb.cov[3], bmer);
         ++alen; nkm += 1; nkmT += rb.nkmT;
         fl |= rb.flags & (NF_TUMOR | NF_NORMAL);
         W.gr[Bj].flags = rb.flags | NF_DEAD;
@@ -2895,25 +2983,9 @@ DEVNI uint32_t compress_fast(Ctx &c, int comp, bool quiet = false) {
       G.seq_lo = lo; G.seq_hi = hi; G.mincov = mn; G.mincovqv = mq;
       G.cov[0] = nc0; G.cov[1] = nc1; G.cov[2] = nc2; G.cov[3] = nc3;
       G.flags = fl; G.nkm = nkm; G.nkmT = nkmT;
-      // ---- the last absorbed node's other edges move to the head (compress_node's tail, unchanged)
+      // ---- the last absorbed node's other edges move to the head
       const uint32_t buddy = list[2 * (cnt - 1)], ed = list[2 * (cnt - 1) + 1];
-      const char bdir = (ed == 0 || ed == 2) ? 'R' : 'F';
-      const int buid = get_buddy(c, buddy, bdir);
-      const int bcnt = (int)W.gr[buddy].necnt;
-      for (int i = 0; i < bcnt; ++i) {
-        if (i == buid) continue;
-        const uint32_t be = W.gr[buddy].edges[i];
-        uint32_t ndir = ED_DIR(be);
-        if (ed == 1 || ed == 2) ndir = flipme(ndir);
-        const uint32_t other = ED_TO(be);
-        const int ec = (int)G.necnt;
-        if (ec >= LC_EMAX) { OVF(c); return 0; }
-        if (other == buddy) { G.edges[ec] = ED_MAKE(H, ndir) | (be & (1u << 30)); G.necnt = ec + 1; }
-        else {
-          G.edges[ec] = ED_MAKE(other, ndir) | (be & (1u << 30)); G.necnt = ec + 1;
-          update_edge(c, other, buddy, fliplink(ED_DIR(be)), H, fliplink(ndir));
-        }
-      }
+      if (!adopt_edges(c, gr_edges(c), H, buddy, get_buddy(c, buddy, link_bdir(ed)), ed)) return 0;
     }
   }
   if (ringed || S.overflow) { S.tmp2 = 0; return clean_dead(c, quiet); }
@@ -2948,6 +3020,56 @@ DEV lc_u4 pr_unpack(unsigned long long v) {
 DEV unsigned long long pr_pack(const lc_u4 r) {
   return (unsigned long long)(r.x == LC_NIL ? 0x1FFFu : r.x) | ((unsigned long long)(r.y & 0x1FFFu) << 13) | ((unsigned long long)(r.z & 0x1FFFu) << 26) | ((unsigned long long)(r.w & 0x1FFFu) << 39) | ((unsigned long long)(r.y >> 31) << 52);
 }
+// ---- the arithmetic on port records, for compress_rank and the build kernel's bl_compress_first.  Port 2 i + sd leaves the node at
+//      position i through its F (sd 0) or R (sd 1) side.
+DEV uint32_t port_cnt(const lc_u4 r) { return r.y & 0x7FFFFFFFu; }                          // nodes beyond the port
+// The record a port starts with: nothing beyond it, or the one node its mergeable link l leads to (n: the node's id, posB: the position
+// of that node, back: that node's link on the side l arrives at).  *irregular is set when `back` is not l's mirror image.
+DEV lc_u4 port_init(uint32_t l, uint32_t back, uint32_t posB, uint32_t n, uint32_t i, uint32_t sd, bool *irregular) {
+  lc_u4 r; r.x = LC_NIL; r.y = 0; r.z = i; r.w = 2u * i + sd;
+  if (l & CL_VALID) {
+    const uint32_t ed = CL_DIR(l);
+    if (!(back & CL_VALID) || CL_TO(back) != n || CL_DIR(back) != fliplink(ed)) *irregular = true;
+    r.x = 2u * posB + (1u - link_side(ed)); r.y = 1u | ((link_flips(ed) ? 1u : 0u) << 31);      // on through the other side of that node
+  }
+  return r;
+}
+// one round of pointer jumping: port r (r.x != LC_NIL) takes over what the port q it points at knows
+DEV lc_u4 port_jump(lc_u4 r, const lc_u4 q) {
+  r.y = ((port_cnt(r) + port_cnt(q)) & 0x7FFFFFFFu) | ((r.y ^ q.y) & 0x80000000u);
+  if (q.z < r.z) r.z = q.z;
+  r.w = q.w; r.x = q.x;
+  return r;
+}
+// a, b: the finished F and R ports of the node at position i.  The chain's head is its member that comes first in the table.
+DEV uint32_t port_cmin(const lc_u4 a, const lc_u4 b) { return a.z < b.z ? a.z : b.z; }
+DEV bool port_is_head(const lc_u4 a, const lc_u4 b, uint32_t i) { return port_cnt(a) + port_cnt(b) > 0 && port_cmin(a, b) == i; }
+DEV uint32_t port_head_side(const lc_u4 a, const lc_u4 b) { return a.z == port_cmin(a, b) ? 0u : 1u; }      // the side of an absorbed node its head lies beyond
+// The place of an absorbed node (ports a, b) in the merges of its head (ports hF, hR); lnk_in: the node's own link on port_head_side.
+struct PortPlace {
+  bool onF;                  // it is merged on the head's F side (compressNode's first loop), else on its R side
+  uint32_t j;                // as the j-th merge of that side, 1 ..
+  uint32_t st_j;             // its frame is the head's, flipped
+  uint32_t edir; bool brev;  // the direction it is entered by, in the frame of the unitig so far (compressNode's edir / brev)
+  uint32_t hmF, hmR;         // merges on the head's F and R side
+};
+DEV PortPlace port_place(const lc_u4 a, const lc_u4 b, const lc_u4 hF, const lc_u4 hR, uint32_t lnk_in) {
+  PortPlace p;
+  const lc_u4 away = port_head_side(a, b) ? a : b;                        // the port that leads away from the head
+  p.onF = away.w == hF.w && port_cnt(hF) > 0;
+  const lc_u4 hp = p.onF ? hF : hR;
+  p.hmF = port_cnt(hF); p.hmR = port_cnt(hR);
+  p.j = port_cnt(hp) - port_cnt(away);
+  p.st_j = ((hp.y ^ away.y) >> 31) & 1u;
+  const uint32_t raw = fliplink(CL_DIR(lnk_in));                          // the link that enters this node, in its predecessor's frame
+  const uint32_t st_p = p.st_j ^ (link_flips(raw) ? 1u : 0u);
+  p.edir = st_p ? flipme(raw) : raw;
+  p.brev = link_brev(p.edir);
+  return p;
+}
+// ... in the head's new deque of K + hmF + hmR descriptors (its own k-mer at hmR) and in its slice of the merge-order list (F side first)
+DEV uint32_t port_deque_slot(const PortPlace &p, int K) { return p.onF ? p.hmR + (uint32_t)K + (p.j - 1u) : p.hmR - p.j; }
+DEV uint32_t port_slice_slot(const PortPlace &p) { return p.onF ? p.j - 1u : p.hmF + p.j - 1u; }
 DEVNI bool compress_rank(Ctx &c, int comp) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
   const int K = S.K;
@@ -2970,15 +3092,10 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
     const uint32_t n = W.order[i];
     for (uint32_t sd = 0; sd < 2; ++sd) {
       const uint32_t l = W.cmp[n].lnk[sd];
-      lc_u4 r; r.x = LC_NIL; r.y = 0; r.z = (uint32_t)i; r.w = 2u * (uint32_t)i + sd;
-      if (l & CL_VALID) {
-        const uint32_t B = CL_TO(l), ed = CL_DIR(l);
-        const uint32_t sb = (ed == 0 || ed == 2) ? 1u : 0u;                 // the side of B the link arrives at ('R' -> 1)
-        const uint32_t back = W.cmp[B].lnk[sb];
-        if (!(back & CL_VALID) || CL_TO(back) != n || CL_DIR(back) != fliplink(ed)) S.tmp3 = 1;      // not the mirror image: leave it to the literal replay
-        r.x = 2u * pos[B] + (1u - sb); r.y = 1u | (((ed == 1 || ed == 2) ? 1u : 0u) << 31);
-      }
-      PA[2u * (uint32_t)i + sd] = pr_pack(r);
+      uint32_t back = 0, pB = 0; bool irr = false;
+      if (l & CL_VALID) { const uint32_t B = CL_TO(l); back = W.cmp[B].lnk[link_side(CL_DIR(l))]; pB = pos[B]; }
+      PA[2u * (uint32_t)i + sd] = pr_pack(port_init(l, back, pB, n, (uint32_t)i, sd, &irr));
+      if (irr) S.tmp3 = 1;                                                  // not the mirror image: leave it to the literal replay
     }
   }
   if (wg_bcast(&S.tmp3)) return false;
@@ -2996,12 +3113,7 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
         for (int u = 0; u < 4; ++u) {
           const int p = p0 + u * LANCET_WG;
           if (p >= NP) continue;
-          if (r[u].x != LC_NIL) {
-            r[u].y = (((r[u].y & 0x7FFFFFFFu) + (q[u].y & 0x7FFFFFFFu)) & 0x7FFFFFFFu) | ((r[u].y ^ q[u].y) & 0x80000000u);
-            if (q[u].z < r[u].z) r[u].z = q[u].z;
-            r[u].w = q[u].w; r[u].x = q[u].x;
-            if (r[u].x != LC_NIL) S.tmp0 = 1;
-          }
+          if (r[u].x != LC_NIL) { r[u] = port_jump(r[u], q[u]); if (r[u].x != LC_NIL) S.tmp0 = 1; }
           Q[p] = pr_pack(r[u]);
         }
       }
@@ -3015,9 +3127,8 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
   SUBPHASE(c, 1, 4);
   WG_FOR(i, M) {
     const lc_u4 a = pr_unpack(P[2 * (size_t)i]), b = pr_unpack(P[2 * (size_t)i + 1]);
-    const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu;
-    const uint32_t cmin = a.z < b.z ? a.z : b.z;
-    const bool head = (mF + mR > 0) && cmin == (uint32_t)i;
+    const uint32_t mF = port_cnt(a), mR = port_cnt(b);
+    const bool head = port_is_head(a, b, (uint32_t)i);
     hs[i] = head ? mF + mR : 0u; al[i] = head ? (uint32_t)K + mF + mR : 0u;
     if (head) { lc_u4 z; z.x = 0x7FFFFFFFu; z.y = 0x7FFFFFFFu; z.z = 0; z.w = 0; stg4(hacc + 4 * (size_t)i, z); hl[dev_atomic_add((LC_LDS uint32_t *)&S.cmp_nh, 1u)] = (uint32_t)i; }
   }
@@ -3032,35 +3143,24 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
   SUBPHASE(c, 1, 5);
   WG_FOR(i, M) {
     const lc_u4 a = pr_unpack(P[2 * (size_t)i]), b = pr_unpack(P[2 * (size_t)i + 1]);
-    const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu;
-    if (mF + mR == 0) continue;
-    const uint32_t cmin = a.z < b.z ? a.z : b.z;
+    if (port_cnt(a) + port_cnt(b) == 0) continue;
+    const uint32_t cmin = port_cmin(a, b);
     const uint32_t n = W.order[i];
     if (cmin == (uint32_t)i) { W.cmp[n].pad[0] = n; W.cmp[n].pad[1] = 0; continue; }       // a head
-    const uint32_t sH = (a.z == cmin) ? 0u : 1u;                            // the head lies beyond this side
-    const lc_u4 away = sH ? a : b;                                          // the port that leads away from the head
-    const lc_u4 hF = pr_unpack(P[2 * (size_t)cmin]), hR = pr_unpack(P[2 * (size_t)cmin + 1]);
-    const bool onF = away.w == hF.w && (hF.y & 0x7FFFFFFFu) > 0;
-    const lc_u4 hp = onF ? hF : hR;
-    const uint32_t mdir = hp.y & 0x7FFFFFFFu, hmF = hF.y & 0x7FFFFFFFu, hmR = hR.y & 0x7FFFFFFFu;
-    const uint32_t j = mdir - (away.y & 0x7FFFFFFFu);                       // 1 .. mdir
-    const uint32_t st_j = ((hp.y ^ away.y) >> 31) & 1u;
     LC_GLOBAL const CmpRec &r = W.cmp[n];
-    const uint32_t raw = fliplink(CL_DIR(r.lnk[sH]));                      // the link that enters this node, in its predecessor's frame
-    const uint32_t st_p = st_j ^ ((raw == 1 || raw == 2) ? 1u : 0u);
-    const uint32_t edir = st_p ? flipme(raw) : raw;
-    const bool brev = (edir == 1 || edir == 3);
+    const PortPlace pp = port_place(a, b, pr_unpack(P[2 * (size_t)cmin]), pr_unpack(P[2 * (size_t)cmin + 1]), r.lnk[port_head_side(a, b)]);
+    const uint32_t st_j = pp.st_j, edir = pp.edir; const bool brev = pp.brev;
     const uint32_t H = W.order[cmin];
     const uint32_t nb = top + al[cmin];                                     // the head's new deque: [nb, nb + K + hmF + hmR), its own k-mer at nb + hmR
-    const uint32_t d = brev ? (r.d0 ^ 3u) : r.dK;
-    if (onF) W.seq[nb + hmR + (uint32_t)K + (j - 1u)] = d; else W.seq[nb + hmR - j] = d ^ 3u;
-    const uint32_t t = hs[cmin] + (onF ? j - 1u : hmF + j - 1u);
+    const uint32_t d = kmer_end_desc(r.d0, r.dK, brev);
+    W.seq[nb + port_deque_slot(pp, K)] = pp.onF ? d : d ^ 3u;
+    const uint32_t t = hs[cmin] + port_slice_slot(pp);
     lc_u4 o0;
     o0.x = __builtin_bit_cast(uint32_t, r.cov[0]); o0.y = __builtin_bit_cast(uint32_t, r.cov[1]); o0.z = __builtin_bit_cast(uint32_t, r.cov[2]); o0.w = __builtin_bit_cast(uint32_t, r.cov[3]);
     stg4(ord + 4 * (size_t)t, o0);
     {                                                                       // what does not depend on the merge order goes straight to the head
       LC_GLOBAL uint32_t *ha = hacc + 4 * (size_t)cmin;
-      dev_atomic_min(&ha[0], (uint32_t)r.tot); dev_atomic_min(&ha[1], (uint32_t)(brev ? r.tq0 : r.tqK));
+      dev_atomic_min(&ha[0], (uint32_t)r.tot); dev_atomic_min(&ha[1], (uint32_t)kmer_end_tq(r.tq0, r.tqK, brev));
       if (r.flags & (NF_TUMOR | NF_NORMAL)) dev_atomic_or(&ha[2], r.flags & (NF_TUMOR | NF_NORMAL));
       if (r.nkmT) dev_atomic_add(&ha[3], r.nkmT);
     }
@@ -3082,7 +3182,7 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
     const uint32_t H = W.order[i];
     LC_GLOBAL NodeGr &G = W.gr[H];
     const lc_u4 a = pr_unpack(P[2 * (size_t)i]), b = pr_unpack(P[2 * (size_t)i + 1]);
-    const uint32_t mF = a.y & 0x7FFFFFFFu, mR = b.y & 0x7FFFFFFFu;
+    const uint32_t mF = port_cnt(a), mR = port_cnt(b);
     const uint32_t nb = top + al[i], olo = G.seq_lo;
     if (lazy && olo == G.nqv * (uint32_t)K) { for (int t = 0; t < K; ++t) W.seq[nb + mR + (uint32_t)t] = seq_desc_lazy(S, H, G.nqv, K, t); }
     else for (int t = 0; t < K; ++t) W.seq[nb + mR + (uint32_t)t] = W.seq[olo + (uint32_t)t];
@@ -3103,17 +3203,12 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
       if (!(side == 0 ? mF : mR)) continue;
       const uint32_t E = W.order[(side == 0 ? a.w : b.w) >> 1];            // the end of the list in that direction
       const uint32_t info = W.cmp[E].pad[1], ed = (info >> 2) & 3u, st = (info >> 1) & 1u;
-      const char bdir = (ed == 0 || ed == 2) ? 'R' : 'F';
-      const int buid = get_buddy(c, E, bdir);
+      const int buid = get_buddy(c, E, link_bdir(ed));
       const int bcnt = (int)W.gr[E].necnt;
       for (int e = 0; e < bcnt; ++e) {
         if (e == buid) continue;
-        const uint32_t be = W.gr[E].edges[e];
-        uint32_t ndir = ED_DIR(be);
-        if (st) ndir = flipme(ndir);
-        const uint32_t other = ED_TO(be);
         if (m >= LC_EMAX) { bad = true; break; }
-        el[m++] = ED_MAKE(other == E ? H : other, ndir) | (be & (1u << 30));
+        el[m++] = adopted_edge(gr_edges(c), W.gr[E].edges[e], st != 0, E, H);
       }
     }
     if (bad) { OVF(c); continue; }
@@ -3126,12 +3221,8 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
   // ---- the float averaging of the merges (Graph.cc:2632-2636), in merge order: the one strictly sequential piece -- a clean window is
   //      ONE chain of ~590 merges, four IEEE divisions each.  The four coverages are independent recurrences: one lane per (head,
   //      coverage) instead of one per head, the next four operands already on their way.
-  // Round 6: the division by the integer t + 2 as (float)((double)numerator * RCP[t]), RCP[t] = 1.0 / (double)(t + 2): that IS the correctly
-  // rounded float quotient -- the double product is off by less than 2^-52 relative (two roundings of 2^-53), while the exact quotient of two
-  // 24-bit floats is either a float or more than 2^-49 relative away from every midpoint between two floats (|A * 2^24 - M * B| >= 1 for an
-  // odd M: B < 2^24 cannot divide it out), so rounding the product to float rounds as the quotient does (no overflow / subnormals: coverages
-  // below 65 536, divisors below 4097).  Five dependent instructions per merge instead of the IEEE division's twelve.  The table is made by
-  // all lanes in the (idle) scratch array.
+  // Round 6: the division by the integer t + 2 as a product with RCP[t] = 1.0 / (double)(t + 2) (merge_cov_rcp, where the proof stands).  The
+  // table is made by all lanes in the (idle) scratch array.
   LC_GLOBAL double *RCP = (LC_GLOBAL double *)W.scratch;
   static_assert(sizeof(double) == 8, "reciprocal table");
   WG_FOR(t, nabs) { RCP[t] = 1.0 / (double)((uint32_t)t + 2u); }
@@ -3143,8 +3234,7 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
     LC_GLOBAL NodeGr &G = W.gr[W.order[i]];
     float nc = G.cov[q];
     LC_GLOBAL const uint32_t *sl = ord + 4 * (size_t)hs[i] + q;
-#define LC_MERGE_STEP(cv, rv, t) do { if ((t) < cnt) { const int amer = (int)(t) + 1, bmer = 1;   /* Graph.cc:2632-2636: same numerator, same order; the division as above */ \
-      const float num = (nc * amer) + (__builtin_bit_cast(float, (cv)) * bmer); nc = (float)((double)num * (rv)); } } while (0)
+#define LC_MERGE_STEP(cv, rv, t) do { if ((t) < cnt) nc = merge_cov_rcp(nc, (int)(t) + 1, __builtin_bit_cast(float, (cv)), (rv)); } while (0)
 #define LC_MERGE_IDX(u, t0) ((size_t)((t0) + (u) < cnt ? (t0) + (u) : cnt - 1))
     uint32_t n0 = sl[4 * LC_MERGE_IDX(0u, 0u)], n1 = sl[4 * LC_MERGE_IDX(1u, 0u)], n2 = sl[4 * LC_MERGE_IDX(2u, 0u)], n3 = sl[4 * LC_MERGE_IDX(3u, 0u)];
     double r0 = RCP[LC_MERGE_IDX(0u, 0u)], r1 = RCP[LC_MERGE_IDX(1u, 0u)], r2 = RCP[LC_MERGE_IDX(2u, 0u)], r3 = RCP[LC_MERGE_IDX(3u, 0u)];
@@ -3178,8 +3268,7 @@ DEVNI bool compress_rank(Ctx &c, int comp) {
       uint32_t ew = head ? ne[13 * (size_t)i + 1 + e] : G.edges[e];
       const uint32_t to = ED_TO(ew);
       if (!(W.gr[to].flags & NF_SPECIAL) && W.todo[to]) {
-        const uint32_t info = W.cmp[to].pad[1];
-        ew = ED_MAKE(W.cmp[to].pad[0], ED_DIR(ew) ^ ((info >> 1) & 1u)) | (ew & (1u << 30));
+        ew = redirected_edge(gr_edges(c), ew, W.cmp[to].pad[0], (W.cmp[to].pad[1] >> 1) & 1u);
       }
       G.edges[e] = ew;
     }
@@ -3338,20 +3427,12 @@ DEVNI int pass_candidates_wg(Ctx &c, int comp, int pass) {            // list ->
         ok = (mq <= LC_CTX(c).P->low_cov_threshold) || ((double)mq <= (LC_CTX(c).P->min_cov_ratio * avgcov)) || (tt == 1.0f && tn == 1.0f);
       } else if (pass == GP_TIPS) ok = (len - K + 1) < max_tip_len;
       else if (pass == GP_LINKS) ok = (len - K + 1) < max_link_len && (double)(int)h1.x <= thr;
-      else {                                                       // a mergeable link on either side (compress_node's conditions)
+      else {                                                       // a link on either side that compress_node would merge
+        const uint32_t loF = link_out(G, n, 'F'), loR = link_out(G, n, 'R');
         ok = false;
-        if (!l0_tandem(G, n)) {
-          const uint32_t ewF = l0_buddy(G, n, 'F'), ewR = l0_buddy(G, n, 'R');
-          const uint32_t bF = ewF != LC_NIL ? ED_TO(ewF) : n, bR = ewR != LC_NIL ? ED_TO(ewR) : n;
-          const GrLine0 BF = gr_line0(&gr[bF]), BR = gr_line0(&gr[bR]);
-          for (int sd = 0; sd < 2; ++sd) {
-            const uint32_t ew = sd == 0 ? ewF : ewR;
-            if (ew == LC_NIL) continue;
-            const uint32_t edir = ED_DIR(ew), bn = ED_TO(ew);
-            const GrLine0 &Bq = sd == 0 ? BF : BR;
-            if (l0_tandem(Bq, bn)) continue;
-            if (l0_buddy(Bq, bn, (edir == 0 || edir == 2) ? 'R' : 'F') != LC_NIL) ok = true;
-          }
+        if (loF | loR) {
+          const GrLine0 BF = gr_line0(&gr[loF ? CL_TO(loF) : n]), BR = gr_line0(&gr[loR ? CL_TO(loR) : n]);
+          ok = (link_back(BF, n, loF) | link_back(BR, n, loR)) != 0;
         }
       }
     }
@@ -3379,119 +3460,6 @@ DEVNI void clean_dead_flags_wg(Ctx &c, bool quiet) {
   WG_LANE0 { S.M = (uint32_t)live; S.ht_elt -= (uint32_t)(M - live); if (!quiet) evt(c, EV_CLEANDEAD, (uint32_t)(M - live)); }
   WG_SYNC();
 }
-// Graph_t::compressNode (reference src/Graph.cc:2486-2706) by the whole wave (round 6; the single-wave window kernel only).  The merges of
-// the passes that follow the first compress join unitigs of a hundred k-mers and more: compress_node copies the absorbed node's
-// descriptors one by one and looks up the coverage minima behind each -- a load, a store and three dependent loads per descriptor on
-// one lane, ~100 us of the ~120 us removeTips took per window.  Here every lane runs the node-level logic on the same values (uniform
-// loads of the two records; only lane 0 stores), and the loops over descriptors -- the copy, the minima, the move of a deque that has
-// no room left -- are shared out over the lanes.  Same merges in the same order, same float operations per merge.
-DEV int l0_buddy_idx(const GrLine0 &g, uint32_t self, char dir) {      // get_buddy on the registers: index of the one edge in direction dir, or -1
-  if (g.flags & NF_SPECIAL) return -1;
-  int ret = -1, cnt = 0; uint32_t ew = 0;
-#define LC_X(i, e) do { if ((uint32_t)(i) < g.necnt && is_dir(ED_DIR(e), dir)) { if (cnt == 0) { ret = (i); ew = (e); } ++cnt; } } while (0)
-  LC_L0_EACH(g, LC_X);
-#undef LC_X
-  if (cnt != 1 || ED_TO(ew) == self) return -1;
-  return ret;
-}
-DEV uint32_t l0_edge(const GrLine0 &g, int idx) {
-  uint32_t r = 0;
-#define LC_X(i, e) do { if ((i) == idx) r = (e); } while (0)
-  LC_L0_EACH(g, LC_X);
-#undef LC_X
-  return r;
-}
-#ifndef LANCET_FAT
-DEVNI void compress_node_wv(Ctx &c, uint32_t node, char dir) {
-  LC_GLOBAL Work &W = *LC_CTX(c).W; LC_WS &S = LC_SREF(c);
-  const int K = wg_uniform(S.K);
-#ifndef LANCET_WAVE_EMU
-  const bool l0 = wg_is_lane0();
-#else
-  const bool l0 = true;
-#endif
-  while (!wg_uniform(S.overflow)) {
-    LC_GLOBAL NodeGr *gn = &W.gr[node];
-    const GrLine0 G = gr_line0(gn);
-    const int uid = wg_uniform(l0_buddy_idx(G, node, dir));
-    if (uid == -1) return;
-    if (wg_uniform((int)l0_tandem(G, node))) return;
-    const uint32_t ew = (uint32_t)wg_uniform((int)l0_edge(G, uid));
-    const uint32_t edir = ED_DIR(ew);
-    const char bdir = (edir == 0 || edir == 2) ? 'R' : 'F';
-    const uint32_t buddy = ED_TO(ew);
-    LC_GLOBAL NodeGr *gb = &W.gr[buddy];
-    const GrLine0 B = gr_line0(gb);
-    if (wg_uniform((int)l0_tandem(B, buddy))) return;
-    const int buid = wg_uniform(l0_buddy_idx(B, buddy, bdir));
-    if (buid == -1) return;
-    const bool brev = dir_dest(edir) == 'R';
-    // second halves of the two records: cov[4] | mincov mincovqv seq_lo seq_hi | seq_clo seq_chi nkm nkmT
-    const lc_u4 nc4 = ldg4((LC_GLOBAL const uint32_t *)gn + 16), nm4 = ldg4((LC_GLOBAL const uint32_t *)gn + 20), ns4 = ldg4((LC_GLOBAL const uint32_t *)gn + 24);
-    const lc_u4 bc4 = ldg4((LC_GLOBAL const uint32_t *)gb + 16), bm4 = ldg4((LC_GLOBAL const uint32_t *)gb + 20), bs4 = ldg4((LC_GLOBAL const uint32_t *)gb + 24);
-    uint32_t lo = (uint32_t)wg_uniform((int)nm4.z), hi = (uint32_t)wg_uniform((int)nm4.w), clo = (uint32_t)wg_uniform((int)ns4.x), chi = (uint32_t)wg_uniform((int)ns4.y);
-    const uint32_t blo = (uint32_t)wg_uniform((int)bm4.z), bhi = (uint32_t)wg_uniform((int)bm4.w);
-    const int alen = (int)(hi - lo), blen = (int)(bhi - blo);
-    const uint32_t tail = (uint32_t)(blen - (K - 1));
-    // seq_reserve: room for `tail` more descriptors behind (dir F) / in front (dir R); else the deque moves to the top of the arena
-    {
-      const uint32_t front = dir == 'F' ? 0u : tail, back = dir == 'F' ? tail : 0u;
-      if (!(lo - clo >= front && chi - hi >= back)) {
-        const uint32_t len = hi - lo, cap = 2 * (len + front + back) + 16;
-        const uint32_t top = (uint32_t)wg_uniform((int)S.seq_top);
-        if (top + cap > LC_CTX(c).C->seq_cap) { if (l0) OVF(c); return; }
-        const uint32_t nlo = top + (cap - len - front - back) / 2 + front;
-        WG_FOR(i, len) { W.seq[nlo + (uint32_t)i] = W.seq[lo + (uint32_t)i]; }
-        if (l0) { S.seq_top = top + cap; gn->seq_clo = top; gn->seq_chi = top + cap; }
-        clo = top; chi = top + cap; lo = nlo; hi = nlo + len;
-      }
-    }
-    // merged = astr + bstr[K-1:]  (dir F: append ; dir R: prepend the reverse complement), and Node_t::computeMinCov over what is appended
-    if (l0) { S.cn_mn = nm4.x; S.cn_mq = nm4.y; }
-    {
-      uint32_t mn = 0x7FFFFFFFu, mq = 0x7FFFFFFFu;
-      WG_FOR(t, tail) {
-        uint32_t d = brev ? W.seq[bhi - 1 - ((uint32_t)(K - 1) + (uint32_t)t)] : W.seq[blo + (uint32_t)(K - 1) + (uint32_t)t];
-        if (brev) d ^= 3u;
-        if (dir == 'F') W.seq[hi + (uint32_t)t] = d; else { d ^= 3u; W.seq[lo - 1 - (uint32_t)t] = d; }
-        int tt, tq; desc_tot(c, d, &tt, &tq);
-        if ((uint32_t)tt < mn) mn = (uint32_t)tt;
-        if ((uint32_t)tq < mq) mq = (uint32_t)tq;
-      }
-      WG_FOR(l, LANCET_WG) { if (mn != 0x7FFFFFFFu) { dev_atomic_min((LC_LDS uint32_t *)&S.cn_mn, mn); dev_atomic_min((LC_LDS uint32_t *)&S.cn_mq, mq); mn = 0x7FFFFFFFu; } }
-    }
-    const uint32_t nmn = (uint32_t)wg_uniform((int)S.cn_mn), nmq = (uint32_t)wg_uniform((int)S.cn_mq);
-    const int amer = alen - K + 1, bmer = blen - K + 1;
-    if (l0) {
-      if (dir == 'F') gn->seq_hi = hi + tail; else gn->seq_lo = lo - tail;
-      if (dir == 'F') { if (lo != nm4.z) gn->seq_lo = lo; } else { if (hi != nm4.w) gn->seq_hi = hi; }      // (the deque moved)
-      gn->mincov = (int)nmn; gn->mincovqv = (int)nmq;
-      gn->nkm = ns4.z + bs4.z; gn->nkmT = ns4.w + bs4.w;
-      const float ncv[4] = {__builtin_bit_cast(float, nc4.x), __builtin_bit_cast(float, nc4.y), __builtin_bit_cast(float, nc4.z), __builtin_bit_cast(float, nc4.w)};
-      const float bcv[4] = {__builtin_bit_cast(float, bc4.x), __builtin_bit_cast(float, bc4.y), __builtin_bit_cast(float, bc4.z), __builtin_bit_cast(float, bc4.w)};
-      for (int q = 0; q < 4; ++q) gn->cov[q] = ((ncv[q] * amer) + (bcv[q] * bmer)) / (amer + bmer);      // Graph.cc:2632-2636
-      gb->flags = B.flags | NF_DEAD;
-      gn->flags = G.flags | (B.flags & (NF_TUMOR | NF_NORMAL));
-      erase_edge_at(c, node, uid);
-      const int bcnt = (int)B.necnt;
-      for (int i = 0; i < bcnt; ++i) {
-        if (i == buid) continue;
-        const uint32_t be = l0_edge(B, i);
-        uint32_t ndir = ED_DIR(be);
-        if (edir == 1 || edir == 2) ndir = flipme(ndir);
-        const uint32_t other = ED_TO(be);
-        const int cnt = (int)gn->necnt;
-        if (cnt >= LC_EMAX) { OVF(c); break; }
-        if (other == buddy) { gn->edges[cnt] = ED_MAKE(node, ndir) | (be & (1u << 30)); gn->necnt = cnt + 1; }
-        else {
-          gn->edges[cnt] = ED_MAKE(other, ndir) | (be & (1u << 30)); gn->necnt = cnt + 1;
-          update_edge(c, other, buddy, fliplink(ED_DIR(be)), node, fliplink(ndir));
-        }
-      }
-    }
-  }
-}
-#endif
 DEVNI void compress_wg(Ctx &c, int comp) {                            // Graph_t::compress, reference src/Graph.cc:2712-2732
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
   const int nc = pass_candidates_wg(c, comp, GP_MERGE);
@@ -5642,8 +5610,8 @@ DEVNI bool load_prebuilt(Ctx &c, int k) {
     WG_LANE0 { S.seq_lazy = 0; }
     // ---- the coverage of the unitig heads: the float averaging of the merges (reference src/Graph.cc:2632-2636) in merge order, which the
     //      build kernel leaves to this wave (round 6: there it held a 512-lane workgroup for 25 us per window on four lanes).  One lane per
-    //      (head, coverage): nc starts as the head's own k-mer's count and takes the merged k-mers' counts one by one,
-    //          nc = ((nc * amer) + (bc * bmer)) / (amer + bmer),  amer = t + 1, bmer = 1   (the reference's expression, IEEE float division).
+    //      (head, coverage): nc starts as the head's own k-mer's count and takes the merged k-mers' counts one by one by merge_cov with
+    //          amer = t + 1, bmer = 1   (the reference's expression, IEEE float division).
     //      The operands come in chunks of LC_COV_CHUNK through LDS (the staging area, idle here): straight from HBM every fourth merge
     //      waited a round trip -- 80 us per window instead of 25.  A head whose slice spans chunks keeps its value in its record in between.
     const uint32_t nch = CH->cov_heads;
@@ -5672,7 +5640,7 @@ DEVNI bool load_prebuilt(Ctx &c, int k) {
           float famer = (float)((int)(lo - st) + 1);                // (amer and amer + bmer as floats: small integers, exactly what the conversions give)
           for (uint32_t g = lo; g < hi; ++g) {
             const float bc = (float)(uint32_t)((ops[g - c0] >> (16 * q)) & 0xFFFFu);
-            nc = ((nc * famer) + bc) / (famer + 1.0f);
+            nc = merge_cov(nc, famer, bc, 1.0f);
             famer += 1.0f;
           }
 #ifndef LANCET_WAVE_EMU
