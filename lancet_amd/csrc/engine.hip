@@ -1135,8 +1135,9 @@ static int lc_submit_body(lancet_engine *e) {
     if (e->dbg) { HIPCHK(e, hipStreamSynchronize(e->stream)); DBG("build_kernel done"); }
     if (e->n_bslots_large) {
       // (grid sized from what the previous batch left on the list -- batches of one scan are alike; the kernel works any list
-      //  off whatever its grid, and a full grid of idle 1024-lane workgroups costs 0.4 ms per batch)
-      const int glarge = e->n_biglist < 0 ? e->n_bslots_large : std::max(8, std::min(e->n_bslots_large, e->n_biglist));
+      //  off whatever its grid, and a full grid of idle 1024-lane workgroups costs 0.4 ms per batch).  Never more workgroups than
+      //  d_blscratch_large has slots for: a workgroup's scratch is slot blockIdx.x, and a batch of fewer than 8 windows has fewer than 8
+      const int glarge = e->n_biglist < 0 ? e->n_bslots_large : std::min(e->n_bslots_large, std::max(8, e->n_biglist));
       hipLaunchKernelGGL(build_kernel_large, dim3(glarge), dim3(bl_large::WG), 0, e->stream, (const lancet_params *)e->d_params.p, (const DevBatch *)e->d_batch.p,
                          (const EngineCaps *)e->d_caps.p, (uint8_t *)e->d_pre.p, (uint8_t *)e->d_blscratch_large.p, (uint32_t *)e->d_counters.p + 8,
                          (unsigned long long *)(e->phase_times ? e->d_blphase.p : nullptr), (uint8_t *)(e->pool_cap ? e->d_prepool.p : nullptr), e->pool_cap, e->ahead_depth, (uint32_t *)e->d_biglist.p);
