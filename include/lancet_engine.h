@@ -339,9 +339,27 @@ int lancet_engine_build_phase_times(lancet_engine *e, const unsigned long long *
  * lancet_trace_format: those events as the text the reference prints (malloc'd, free with lancet_free); idx1 = the running
  * number of the window ("== Processing N:"), hdr / chrom / start / end = the window's name and coordinates. */
 int lancet_engine_set_trace(lancet_engine *e, uint32_t words_per_window);
+/* The same with a trace level.  Level 1 is lancet_engine_set_trace.  Level 2 adds what the reference prints under -V / --more-verbose
+ * (src/Graph.cc:328-332, :539, :2030-2034, :2168-2213, :800-802): reads that run through a k-mer twice, the reference pseudo-read's id, what
+ * markRefEnds looked at and which nodes it cut off in front of the source and behind the sink, and per path the trimmed window reference and
+ * the path's string.  A DIAGNOSTICS mode, not a throughput mode: those lines come from steps the LDS build kernel otherwise does, so while
+ * level 2 is set every graph takes the general build (as under LANCET_NO_PREBUILD; no graphs built ahead, no build service).  Records, window
+ * stats and the level-1 lines are those of a run without it.  Path strings are long: size words_per_window from the batch (lancet_gpu, per
+ * batch: 512 words, 32 paths of (longest window reference + max_indel_len + 256) bases at a quarter word per base, 16 words per reference
+ * base for the cycle lines).  At level 2 a window whose events
+ * do not fit is not cut silently: evt_len[w] == words_per_window marks it, the last eight words of its buffer say how many words hold events
+ * (lancet_trace_format2 prints them and a line "[trace truncated: ...]").  Level 2 needs words_per_window >= 16 (or 0 = off); LANCET_E_ARG
+ * otherwise and for a level other than 1 or 2.  lancet_engine_trace_level: the level of the engine's next / last upload (0: tracing off). */
+int lancet_engine_set_trace_level(lancet_engine *e, uint32_t words_per_window, int32_t level);
+int lancet_engine_trace_level(const lancet_engine *e);
 int lancet_engine_trace(lancet_engine *e, const uint32_t **evt_len, const uint32_t **evt, uint32_t *words_per_window);
 char *lancet_trace_format(const uint32_t *words, uint32_t n_words, int32_t idx1, const char *hdr, const char *chrom,
                           int32_t start, int32_t end, int32_t dfs_limit);
+/* lancet_trace_format for a level-2 trace: words_per_window as given to lancet_engine_set_trace_level (n_words == words_per_window is the
+ * truncation mark), rawseq / rawseq_len = the window's Ref_t::rawseq (lancet_window_batch::ref_bases of the window), which the level-2
+ * events refer to by offset.  With the events of a level-1 trace the text is lancet_trace_format's. */
+char *lancet_trace_format2(const uint32_t *words, uint32_t n_words, uint32_t words_per_window, int32_t idx1, const char *hdr, const char *chrom,
+                           int32_t start, int32_t end, int32_t dfs_limit, const char *rawseq, uint32_t rawseq_len);
 
 /* ---- test hook: the device global_align_aff (reference src/align.cc:235-364) alone, on one pair of ACGT strings ----------
  * S has 1..1024 bases, T 1..16383 (the traceback keeps positions of T in 14 bits; longer: LANCET_E_ARG).  The aligned rows go to

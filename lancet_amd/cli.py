@@ -10,7 +10,9 @@ The VCF is byte-identical to the reference's for the same inputs (tests/test_cli
 
 -R / --kmer-recovery as in the reference (lancet_params.kmer_recovery); refused together with --linked-reads before any work is done.
 
-Not offered: --bed, --rg-file, --print-graph (graph dumps), --num-threads (accepted, ignored)."""
+Not offered: --bed, --rg-file, --print-graph (graph dumps), --num-threads (accepted, ignored); -V / --more-verbose is refused here -- the
+level-2 trace is lancet_gpu's option (and engine.Engine(trace_level=2) for a caller of the binding); tests/test_recovery_emu.py and
+tests/test_more_verbose_emu.py pin this parser."""
 from __future__ import annotations
 
 import argparse

@@ -311,6 +311,8 @@ struct lancet_engine {
   int build_slots_env = 0, ahead_depth_env = -1;
   int pre_wide_env = -1;           // LANCET_PRE_WIDE=0 / 1: the narrow / wide form of the hand-off areas whatever the batch looks like
   uint32_t evt_cap = 0;
+  uint32_t evt_level = 1;     // lancet_engine_set_trace_level: 2 = the -V lines too, every graph through the general build (prebuild / svc off while it is set)
+  bool lvl_saved = false, prebuild_cfg = true, svc_cfg = true;   // ... what prebuild / svc were before level 2 switched them off
   size_t mem_budget = (size_t)96 << 30;
   int max_slots = 5120;      // work-space slots = resident single-wave workgroups: 5 per SIMD (96 VGPRs, < 8 KB LDS each) x 4 SIMDs x CUs
   uint32_t max_nodes_limit = 65536; bool max_nodes_env = false;
@@ -487,7 +489,20 @@ void lancet_engine_destroy(lancet_engine *e) {
 const char *lancet_engine_last_error(const lancet_engine *e) { return e ? e->err.c_str() : (lc_create_err().empty() ? "null engine" : lc_create_err().c_str()); }
 
 // debug knob used by the tests: number of 32-bit trace words kept per window (0 = off)
-int lancet_engine_set_trace(lancet_engine *e, uint32_t words_per_window) { if (!e) return LANCET_E_ARG; e->evt_cap = words_per_window; return LANCET_OK; }
+int lancet_engine_set_trace(lancet_engine *e, uint32_t words_per_window) { return lancet_engine_set_trace_level(e, words_per_window, 1); }
+// level 2: the events of the reference's -V lines as well.  They come from steps the LDS build kernel otherwise does (its occurrence passes,
+// markRefEnds inside its first compress), so every graph takes the general build while the level is set, as under LANCET_NO_PREBUILD: a
+// diagnostics mode.  Records, window stats and the level-1 events do not depend on the build route.
+int lancet_engine_set_trace_level(lancet_engine *e, uint32_t words_per_window, int32_t level) {
+  if (!e || (level != 1 && level != 2)) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_trace_level while a batch is in flight"; return LANCET_E_STATE; }
+  if (level == 2 && words_per_window && words_per_window < 16) { e->err = "set_trace_level: level 2 needs at least 16 words per window (eight are kept for the truncation mark)"; return LANCET_E_ARG; }
+  if (!e->lvl_saved) { e->prebuild_cfg = e->prebuild; e->svc_cfg = e->svc; e->lvl_saved = true; }
+  const bool l2 = level == 2 && words_per_window != 0;
+  e->evt_cap = words_per_window; e->evt_level = l2 ? 2u : 1u;
+  e->prebuild = l2 ? false : e->prebuild_cfg; e->svc = l2 ? false : e->svc_cfg;
+  return LANCET_OK;
+}
 
 static int up(lancet_engine *e, DevBuf &b, const void *src, size_t bytes) {
   if (b.ensure(bytes ? bytes : 1)) { e->err = "hipMalloc failed"; return LANCET_E_OOM; }
@@ -561,6 +576,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
       e->caps2.var_cap = e->caps.var_cap; e->caps2.blob_cap = e->caps.blob_cap; e->caps2.bx_cap = e->caps.bx_cap;
     }
   }
+  e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
 }
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk) {
   if (!e || !b || b->n_windows < 0) return LANCET_E_ARG;
@@ -1406,6 +1422,8 @@ int lancet_engine_trace(lancet_engine *e, const uint32_t **evt_len, const uint32
   *evt_len = e->evt_len.data(); *evt = e->evt.data(); *words_per_window = e->caps.evt_cap;
   return LANCET_OK;
 }
+
+int lancet_engine_trace_level(const lancet_engine *e) { return (e && e->evt_cap) ? (int)e->evt_level : 0; }
 
 // test hook: runs the device alignment on (S, T) (ACGT strings, |S| <= LC_MAXW, |T| <= LC_NOTE_JMAX); writes the aligned strings.
 // mode 0: band first, full matrix when the band is not certified (what the window kernel does); 1: full matrix only; 2: band only

@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "layout.h"
@@ -127,6 +128,10 @@ static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_
   c.max_w = lc_max_w_for_sizes(bs);              // (a window above LC_MAXW is reported LANCET_W_OVERFLOW on its own)
   c.path_cap = c.max_w + (uint32_t)p->max_indel_len + 256;
   c.evt_cap = evt_cap;
+  // trace level: 1 = -v; 2 = -V as well (the engine sets it from lancet_engine_set_trace_level; LANCET_TRACE_LEVEL=2 in the environment is how the
+  // host emulation of the kernels is told, as it is told LANCET_NO_PREBUILD -- level 2 needs at least 16 words per window, see kernels.h evt_truncate)
+  c.evt_level = evt_cap ? 1u : 0u;
+  if (evt_cap >= 16u) { const char *lv = getenv("LANCET_TRACE_LEVEL"); if (lv && atoi(lv) == 2) c.evt_level = 2u; }
   // Records of the whole batch.  A scan emits ~0.7 per window; permissive settings (--low-cov 0 on noisy reads) reach several
   // hundred per window (fuzz case 7122: 355), and a small batch has no other windows to average that out: 64 per window and
   // a floor of 64 Ki records (lancet_variant is 64 bytes: 140 MB for a 32768-window batch).

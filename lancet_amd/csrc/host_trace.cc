@@ -14,7 +14,9 @@ namespace {
 enum { EV_PROCESS = 1, EV_REPEAT_REF, EV_NEAR_REF, EV_READS, EV_STATS, EV_MARKREF, EV_LOWCOV, EV_CLEANDEAD, EV_COMPRESS, EV_CC,
        EV_CCID, EV_CCEND, EV_TRIM, EV_AMBIG_SRC, EV_NOMATCH_SRC, EV_AMBIG_SNK, EV_NOMATCH_SNK, EV_CYCLE, EV_TIPS_ROUND,
        EV_TIPS_REMOVED, EV_LINKS, EV_LOOKREP, EV_MISSING, EV_SEARCH, EV_NEAR_QRY, EV_DFSLIMIT, EV_PATH, EV_TS, EV_PATH_END,
-       EV_EKA_END, EV_FOUND, EV_END };
+       EV_EKA_END, EV_FOUND, EV_END,
+       // trace level 2 (the reference's -V lines; kernels.h)
+       EV_REFID, EV_RCYC_READ, EV_RCYC, EV_LOOKING, EV_CHK_SRC, EV_RM_SRC, EV_CHK_SNK, EV_RM_SNK, EV_ALN, EV_TRUNC };
 
 void put(std::string &o, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void put(std::string &o, const char *fmt, ...) {
@@ -36,7 +38,24 @@ std::string take_bytes(const uint32_t *w, uint32_t nw, uint32_t *at, uint32_t n)
 
 extern "C" char *lancet_trace_format(const uint32_t *words, uint32_t n_words, int32_t idx1, const char *hdr, const char *chrom,
                                      int32_t start, int32_t end, int32_t dfs_limit) {
+  return lancet_trace_format2(words, n_words, 0u, idx1, hdr, chrom, start, end, dfs_limit, nullptr, 0u);
+}
+
+// The level-2 events refer to Ref_t::rawseq by offset; a level-1 stream holds none of them and words_per_window = 0 says that n_words is never
+// a truncation mark, so lancet_trace_format is this function.
+extern "C" char *lancet_trace_format2(const uint32_t *words, uint32_t n_words, uint32_t words_per_window, int32_t idx1, const char *hdr, const char *chrom,
+                                      int32_t start, int32_t end, int32_t dfs_limit, const char *rawseq, uint32_t rawseq_len) {
   std::string out;
+  // a truncated level-2 window: its buffer is full, EV_TRUNC in the last eight words says how many words hold whole events (kernels.h evt_truncate)
+  bool truncated = false;
+  if (words_per_window >= 16 && n_words == words_per_window && words[words_per_window - 8] == (uint32_t)EV_TRUNC) {
+    truncated = true; n_words = words[words_per_window - 7] <= words_per_window - 8 ? words[words_per_window - 7] : words_per_window - 8;
+  }
+  const auto raw = [&](uint32_t off, uint32_t len) -> std::string {
+    if (!rawseq || off >= rawseq_len) return std::string();
+    return std::string(rawseq + off, rawseq + off + (len < rawseq_len - off ? len : rawseq_len - off));
+  };
+  std::string cyc_read;
   std::vector<uint32_t> ccids;
   uint32_t cc_nodes = 0;
   uint32_t i = 0;
@@ -99,9 +118,20 @@ extern "C" char *lancet_trace_format(const uint32_t *words, uint32_t n_words, in
         if (c) out += " Found cycle in assembly\n";
         out += "FINISHED\n";
         break;
+      case EV_REFID: put(out, "refid: %u\n", a); break;
+      case EV_RCYC_READ: cyc_read = c ? raw(0, b) : take_bytes(words, n_words, &i, b); break;
+      case EV_RCYC: put(out, "cycle detected in read %u offset: %u : ", a, b); out += cyc_read; out.push_back('\n'); break;
+      case EV_LOOKING: put(out, "Looking at %s %u ", hdr, b); out += raw(a, b); out.push_back('\n'); break;
+      case EV_CHK_SRC: out += "checking for other source edges\n"; break;
+      case EV_CHK_SNK: out += "checking for other sink edges\n"; break;
+      case EV_RM_SRC: out += "  removing node before source: "; out += take_bytes(words, n_words, &i, a); out.push_back('\n'); break;
+      case EV_RM_SNK: out += "  removing node after sink: "; out += take_bytes(words, n_words, &i, a); out.push_back('\n'); break;
+      case EV_ALN: out += "alignment\nr:  "; out += raw(a, b); out += "\np:  "; out += take_bytes(words, n_words, &i, c); out.push_back('\n'); break;
       default: break;
     }
   }
+  if (truncated && !out.empty() && out.back() != '\n') out.push_back('\n');      // (a line of its own, also after a line whose end was cut)
+  if (truncated) put(out, "[trace truncated: window %d needs more than %u trace words]\n", idx1, words_per_window);
   char *r = (char *)malloc(out.size() + 1);
   if (!r) return nullptr;
   memcpy(r, out.c_str(), out.size() + 1);

@@ -32,7 +32,17 @@ enum {
   EV_PROCESS = 1, EV_REPEAT_REF, EV_NEAR_REF, EV_READS, EV_STATS, EV_MARKREF, EV_LOWCOV, EV_CLEANDEAD,
   EV_COMPRESS, EV_CC, EV_CCID, EV_CCEND, EV_TRIM, EV_AMBIG_SRC, EV_NOMATCH_SRC, EV_AMBIG_SNK, EV_NOMATCH_SNK,
   EV_CYCLE, EV_TIPS_ROUND, EV_TIPS_REMOVED, EV_LINKS, EV_LOOKREP, EV_MISSING, EV_SEARCH, EV_NEAR_QRY,
-  EV_DFSLIMIT, EV_PATH, EV_TS, EV_PATH_END, EV_EKA_END, EV_FOUND, EV_END
+  EV_DFSLIMIT, EV_PATH, EV_TS, EV_PATH_END, EV_EKA_END, EV_FOUND, EV_END,
+  // trace level 2 only (EngineCaps::evt_level; the reference's -V / --more-verbose lines).  Strings travel as ASCII bytes after the event
+  // (evt_ascii), so that no word of them reads as one of the codes above.
+  EV_REFID,                  // a = index of the reference pseudo-read in readid2info ("refid: ")
+  EV_RCYC_READ,              // a = read, b = its trimmed length, c = 1 for the reference pseudo-read (no bytes: the host has rawseq), else bytes: the trimmed read
+  EV_RCYC,                   // a = read, b = offset: "cycle detected in read" (one per k-mer start the read has met before), after its EV_RCYC_READ
+  EV_LOOKING,                // a, b = Ref_t::seq as (offset into rawseq, length): "Looking at"
+  EV_CHK_SRC, EV_RM_SRC,     // "checking for other source edges" ; "  removing node before source: ": a = length, bytes: the node's id
+  EV_CHK_SNK, EV_RM_SNK,     // the same at the sink
+  EV_ALN,                    // a, b = Ref_t::seq as above, c = length of the path string, bytes: the path string ("alignment", "r:  ", "p:  ")
+  EV_TRUNC                   // the window's events did not fit: a = words that were written; kept in the LAST eight words of the window's buffer
 };
 
 struct WalkState { int nts, last_col, code; };   // the transcript walk's column rule (walk_column): its state from one column to the next
@@ -193,11 +203,24 @@ template <class P> DEV int wg_bcast(P p) {
 }
 template <class P> DEV uint32_t wg_bcastu(P p) { return (uint32_t)wg_bcast(p); }
 
+// Trace level 2 (the reference's -V): a window whose events do not fit says so.  The last eight words of its buffer are kept for EV_TRUNC;
+// the first event that does not fit writes it and closes the stream (evt_len = evt_cap: nothing fits after that, and only a truncated
+// stream has that length).  Level 1 is as it was: an event that does not fit is dropped, a later, shorter one may still be written.
+DEV uint32_t evt_room(Ctx &c) { const uint32_t cap = LC_CTX(c).C->evt_cap; return LC_CTX(c).C->evt_level >= 2u ? cap - 8u : cap; }
+DEV bool evt_l2(Ctx &c) { return LC_CTX(c).C->evt_cap != 0 && LC_CTX(c).C->evt_level >= 2u; }
+DEVNI void evt_truncate(Ctx &c) {
+  LC_WS &S = LC_SREF(c);
+  const uint32_t cap = LC_CTX(c).C->evt_cap;
+  if (LC_CTX(c).C->evt_level < 2u || S.evt_len >= cap) return;
+  uint32_t *p = LC_CTX(c).W->evt + (cap - 8u);
+  p[0] = EV_TRUNC; p[1] = S.evt_len; for (int i = 2; i < 8; ++i) p[i] = 0;
+  S.evt_len = cap;
+}
 // (the record is written out of line: inlined at its ~60 call sites the eight operands were what the window kernel spilled -- 142 VGPRs,
 //  all on paths that run with tracing on only)
 DEVNI void evt_write(Ctx &c, uint32_t code, uint32_t a, uint32_t b, uint32_t d, uint32_t e, uint32_t f, uint32_t g, uint32_t h) {
   LC_WS &S = LC_SREF(c);
-  if (S.evt_len + 8 > LC_CTX(c).C->evt_cap) return;
+  if (S.evt_len + 8 > evt_room(c)) { evt_truncate(c); return; }
   uint32_t *p = LC_CTX(c).W->evt + S.evt_len;
   p[0] = code; p[1] = a; p[2] = b; p[3] = d; p[4] = e; p[5] = f; p[6] = g; p[7] = h;
   S.evt_len += 8;
@@ -211,9 +234,19 @@ DEV void evt_bytes(Ctx &c, const uint8_t *s, uint32_t n) {   // raw bytes append
   if (!LC_CTX(c).C->evt_cap) return;
   LC_WS &S = LC_SREF(c);
   uint32_t words = ((n + 3) / 4 + 7) / 8 * 8;
-  if (S.evt_len + words > LC_CTX(c).C->evt_cap) return;
+  if (S.evt_len + words > evt_room(c)) { evt_truncate(c); return; }
   uint8_t *p = (uint8_t *)(LC_CTX(c).W->evt + S.evt_len);
   for (uint32_t i = 0; i < words * 4; ++i) p[i] = i < n ? s[i] : 0;
+  S.evt_len += words;
+}
+// level 2: an event and, after it, a string of n characters get(0) .. get(n - 1) (ASCII), padded to 8 words; both or neither
+template <class F> DEV void evt_ascii(Ctx &c, uint32_t code, uint32_t a, uint32_t b, uint32_t d, uint32_t n, F get) {
+  LC_WS &S = LC_SREF(c);
+  const uint32_t words = ((n + 3) / 4 + 7) / 8 * 8;
+  if (S.evt_len + 8 + words > evt_room(c)) { evt_truncate(c); return; }
+  evt_write(c, code, a, b, d, 0, 0, 0, 0);
+  uint8_t *p = (uint8_t *)(LC_CTX(c).W->evt + S.evt_len);
+  for (uint32_t i = 0; i < words * 4; ++i) p[i] = i < n ? (uint8_t)get((int)i) : (uint8_t)0;
   S.evt_len += words;
 }
 
@@ -3672,14 +3705,75 @@ DEVNI void mark_ref_scan(Ctx &c, int comp) {
   }
   WG_LANE0 { S.mr_snk = ko; }
 }
+// Trace level 2: Node_t::nodeid_m of a node in an event -- the canonical k-mer the node was made for (it keeps that id through every merge),
+// for a reference k-mer with N its canonical string; the name of a source / sink node.
+DEVNI void evt_node_id(Ctx &c, uint32_t code, uint32_t n) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const int K = S.K;
+  if (n >= LC_CTX(c).C->node_cap) {                                   // (special_new's names)
+    const bool src = (W.gr[n].flags & NF_SOURCE) != 0; const int pl = src ? 6 : 4, comp = W.gr[n].comp;
+    int nd = 1; for (int v = comp; v >= 10; v /= 10) ++nd;
+    evt_ascii(c, code, (uint32_t)(pl + nd), 0, 0, (uint32_t)(pl + nd), [&](int j) -> int {
+      if (j < pl) return (int)(src ? "source" : "sink")[j];
+      int v = comp; for (int q = pl + nd - 1; q > j; --q) v /= 10;
+      return '0' + v % 10; });
+    return;
+  }
+  LC_GLOBAL const unsigned long long *k = W.nkey + (size_t)n * LC_NWMAX;
+  if (S.hasN && (W.gr[n].flags & NF_NKMER)) {
+    LC_GLOBAL const uint8_t *refc = LC_CTX(c).B->ref_codes + LC_CTX(c).B->ref_off[S.w];
+    const int p = (int)(k[0] >> 1); const bool isR = (k[0] & 1ULL) != 0;
+    evt_ascii(c, code, (uint32_t)K, 0, 0, (uint32_t)K, [&](int j) -> int { return (int)"ACGTN"[nk_char(refc, p, K, isR, j)]; });
+  } else evt_ascii(c, code, (uint32_t)K, 0, 0, (uint32_t)K, [&](int j) -> int { return (int)"ACGT"[key_base(k, K, j)]; });
+}
+// Trace level 2: loadSequence's "cycle detected in read" lines (reference src/Graph.cc:328-332) of the build just made, in buildgraph's order
+// (:542-569: the reads by index, the reference pseudo-read last; a read's k-mer starts in turn).  Start p of a read is reported (as offset
+// p - 1) when an earlier start of the same read has the same node.  64 reads at a time: a lane looks whether its read has such a start at
+// all, lane 0 then writes the events of the reads that have.  Diagnostics: quadratic in a read's k-mers.
+DEVNI void trace_read_cycles(Ctx &c) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const int R = wg_bcast(&S.R);
+  WG_LANE0 { if (S.n_builds == 1) evt(c, EV_REFID, (uint32_t)(R - 1)); }
+  for (int r0 = 0; r0 < R; r0 += 64) {
+    WG_FOR(l, 64) {
+      const int r = r0 + l; uint32_t hit = 0;
+      if (r < R) {
+        const uint32_t b = W.occ_base[r], n = W.occ_base[r + 1] - b;
+        for (uint32_t p = 1; p < n && !hit; ++p) {
+          const uint32_t t = W.occ[b + p] & 0x3FFFFFFFu;
+          for (uint32_t q = 0; q < p; ++q) if ((W.occ[b + q] & 0x3FFFFFFFu) == t) { hit = 1; break; }
+        }
+      }
+      S.part2[l] = hit;
+    }
+    WG_SYNC();
+    WG_LANE0 {
+      for (int l = 0; l < 64 && r0 + l < R; ++l) {
+        if (!S.part2[l]) continue;
+        const int r = r0 + l;
+        uint32_t rinfo, bw, gw; int tlen; bool isref;
+        read_geom(c, r, &rinfo, &bw, &gw, &tlen, &isref);
+        if (isref) evt(c, EV_RCYC_READ, (uint32_t)r, (uint32_t)tlen, 1u);
+        else evt_ascii(c, EV_RCYC_READ, (uint32_t)r, (uint32_t)tlen, 0u, (uint32_t)tlen, [&](int j) -> int { return (int)"ACGT"[read_base(c, false, bw, j)]; });
+        const uint32_t b = W.occ_base[r], n = W.occ_base[r + 1] - b;
+        for (uint32_t p = 1; p < n; ++p) {
+          const uint32_t t = W.occ[b + p] & 0x3FFFFFFFu;
+          for (uint32_t q = 0; q < p; ++q) if ((W.occ[b + q] & 0x3FFFFFFFu) == t) { evt(c, EV_RCYC, (uint32_t)r, p - 1u); break; }
+        }
+      }
+    }
+  }
+}
 // markRefEnds (reference src/Graph.cc): source / sink creation by lane 0, their insertion into the table order by the wave.
 DEVNI void mark_ref_ends(Ctx &c, int comp) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
   const int K = S.K;
+  const bool l2 = evt_l2(c);                                   // (read once: the level-2 lines of this function)
   WG_LANE0 {
     S.tmp2 = (int)LC_NIL;                                      // node to insert next (LC_NIL: stop)
     S.trim5 = 0xFFFF; S.trim3 = 0xFFFF;
     S.source = LC_NIL; S.sink = LC_NIL;
+    if (l2) evt(c, EV_LOOKING, (uint32_t)S.seq_t5, (uint32_t)S.seq_len);
     // the scans over the reference offsets ran in mark_ref_scan (same predicates, same outcome order)
     if (S.mr_src >= 0 && S.mr_ambs) evt(c, EV_AMBIG_SRC);
     else if (S.mr_src < 0) evt(c, EV_NOMATCH_SRC);
@@ -3704,10 +3798,12 @@ DEVNI void mark_ref_ends(Ctx &c, int comp) {
       if (ns != LC_NIL) {
         uint32_t sourcedir = src_ori ? 1u : 0u;                              // FF, or FR when the k-mer is reversed
         char flip = src_ori ? 'F' : 'R';                                     // Edge_t::flipdir(source_mer.ori_m)
+        if (l2) evt(c, EV_CHK_SRC);
         for (int i = (int)W.gr[src].necnt - 1; i >= 0; --i) {
           uint32_t e = W.gr[src].edges[i];
           if (dir_start(ED_DIR(e)) == flip) {
             uint32_t other = ED_TO(e);
+            if (l2 && other != src) evt_node_id(c, EV_RM_SRC, other);
             if (other != src) { remove_edge(c, other, src, fliplink(ED_DIR(e))); erase_edge_at(c, src, i); }
           }
         }
@@ -3732,10 +3828,12 @@ DEVNI void mark_ref_ends(Ctx &c, int comp) {
     if (nk != LC_NIL) {
       uint32_t sinkdir = snk_ori ? 0u : 3u;                                // RR, or FF when reversed
       char same = snk_ori ? 'R' : 'F';
+      if (l2) evt(c, EV_CHK_SNK);
       for (int i = (int)W.gr[snk].necnt - 1; i >= 0; --i) {
         uint32_t e = W.gr[snk].edges[i];
         if (dir_start(ED_DIR(e)) == same) {
           uint32_t other = ED_TO(e);
+          if (l2 && other != snk) evt_node_id(c, EV_RM_SNK, other);
           if (other != snk) { remove_edge(c, other, snk, fliplink(ED_DIR(e))); erase_edge_at(c, snk, i); }
         }
       }
@@ -5337,6 +5435,9 @@ DEVNI void count_ref_path(Ctx &c) {
         WG_LANE0 {
           S.part[5] = (uint32_t)m; S.part[6] = need_align ? 1u : 0u;
           if (!need_align) S.part[7] = (uint32_t)n;
+          // level 2: processPath's "alignment" / "r:" / "p:" lines (reference src/Graph.cc:800-802) are printed before the Hamming test, for every
+          // path: written here, once per path and above both walk drivers, a path that is redone after WALK_FULL included
+          if (evt_l2(c) && !S.overflow) evt_ascii(c, EV_ALN, (uint32_t)S.seq_t5, (uint32_t)n, (uint32_t)m, (uint32_t)m, [&](int j) -> int { return (int)"ACGT"[W.pseq[j] & 3]; });
           if (n > (int)LC_CTX(c).C->max_w || n < 1 || m < 1) OVF(c);
           if (S.overflow) S.part[3] = 1;
         }
@@ -5839,6 +5940,7 @@ DEV void process_window(Ctx &c, int w, int rq = -1) {
       build_graph(c);
     }
     if (wg_bcast(&S.overflow)) break;
+    if (evt_l2(c)) trace_read_cycles(c);                          // (level 2 takes the general build for every graph: occ[] holds this build's nodes)
     PHASE(c, 7);
     const bool pre_order = wg_bcast(&S.pre_order) != 0;
     if (!pre_order) first_lowcov(c);

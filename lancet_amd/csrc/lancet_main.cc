@@ -20,6 +20,9 @@
 // lancet_host_batch_packed -> lancet_engine_upload_packed as without the option.  One stderr line at the end counts both, by reason.
 // Not offered: --print-graph; --num-threads is accepted and ignored (windows are
 // batched on the GPU); -v prints the reference's per-window stage trace to stderr.
+// -V / --more-verbose: -v plus the reference's -V lines (lancet_engine_set_trace_level, level 2): a diagnostics mode, every graph through the
+// general build.  The trace buffer is sized per batch (trace_words_for); windows whose trace did not fit say so in the text and are counted
+// on stderr.  The VCF is the one without the flag.
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
 
@@ -50,8 +53,16 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
+// -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
+// up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
+// base for the reads that run through a k-mer twice (8 words per line, the read once).  A window that needs more says so in its trace.
+const uint32_t MV_PATHS = 32;
+uint32_t trace_words_for(uint32_t longest, int max_indel_len) {
+  const uint32_t w = 512u + MV_PATHS * ((longest + (uint32_t)max_indel_len + 256u + 3u) / 4u + 16u) + 16u * longest;
+  return (w + 7u) / 8u * 8u;
+}
 int die(const std::string &m) { fprintf(stderr, "lancet_gpu: %s\n", m.c_str()); return 1; }
 void usage() {
   fputs("Usage: lancet_gpu --tumor T.bam --normal N.bam --ref ref.fa (--reg chr:start-end | --bed regions.bed) [options] > out.vcf\n"
@@ -61,7 +72,10 @@ void usage() {
         "   --num-threads, -X  <int>   : accepted and ignored (windows are batched on the GPU)\n"
         "   --kmer-recovery, -R        : as in the reference (tumour k-mers seen once lend their occurrence to well-supported k-mers one\n"
         "                                low-quality base away); not together with --linked-reads\n"
-        "   --print-graph, --node-str-len, --more-verbose, --print-config-file: not offered\n"
+        "   --more-verbose, -V         : -v plus the reference's -V lines: reads that run through a k-mer twice, what markRefEnds looked at and\n"
+        "                                cut off, the reference and the path string of every path.  DIAGNOSTICS, not a throughput mode: every graph\n"
+        "                                takes the general build (no LDS build kernel, no graphs built ahead); same VCF as without it\n"
+        "   --print-graph, --node-str-len, --print-config-file: not offered\n"
         "Additional options:\n"
         "   --device <n> | --devices a,b,...  : GPU(s) to use; an entry may repeat (two engines on one GPU overlap the upload of a\n"
         "                                       batch with the kernels of the previous one)\n"
@@ -84,7 +98,7 @@ int main(int argc, char **argv) {
   std::string tumor, normal, ref, reg, bed, qrange = "!", date_line, devices, rg_file;
   int min_k = 11, max_k = 101, trim_lowqual = 10, min_base_qual = 17, tip_len = 11, cov_thr = 5, low_cov = 1, dfs_limit = 1000000;
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
-  int device = 0, batch_windows = 8192, verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
+  int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
   std::string rendezvous;
   double cov_ratio = 0.01;
@@ -115,7 +129,7 @@ int main(int argc, char **argv) {
     else if (L == "min-strand-bias") flt.min_strand_bias = (int)atof(v); else if (L == "max-unit-length") max_unit_length = atoi(v);
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
-    else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
+    else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
     else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
@@ -198,7 +212,7 @@ int main(int argc, char **argv) {
     const int rc = lancet_engine_create(&P, d, &e);
     if (rc == LANCET_E_UNSUPPORTED) return die("unsupported parameters: --max-k must be <= 127, --min-k >= 3, --max-unit-length <= 8");
     if (rc != LANCET_OK) return die(std::string("cannot create the MI355X engine on device ") + std::to_string(d) + " (code " + std::to_string(rc) + "): " + (e ? lancet_engine_last_error(e) : "no gfx950 device / HIP runtime"));
-    if (verbose) lancet_engine_set_trace(e, 1u << 17);            // -v: the reference's per-window stage trace, to stderr
+    if (verbose && !more_verbose) lancet_engine_set_trace(e, 1u << 17);            // -v: the reference's per-window stage trace, to stderr (-V: set per batch, below)
     engs.push_back(e);
   }
   char err[512] = "";
@@ -224,12 +238,13 @@ int main(int argc, char **argv) {
   // of its kernels overlap with batch i (what `--devices 0,0` asks for explicitly; bench.py --in-flight 2 measures it)
   if (devices.empty() && nchunks > 1 && engs.size() == 1) {
     lancet_engine *e2 = nullptr;
-    if (lancet_engine_create(&P, devs[0], &e2) == LANCET_OK) { if (verbose) lancet_engine_set_trace(e2, 1u << 17); engs.push_back(e2); }
+    if (lancet_engine_create(&P, devs[0], &e2) == LANCET_OK) { if (verbose && !more_verbose) lancet_engine_set_trace(e2, 1u << 17); engs.push_back(e2); }
   }
   struct Job { bool have = false; std::string trace; std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
-  struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn; };
+  struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
+                std::vector<std::string> raw; /* -V: Ref_t::rawseq of the batch's window w (the level-2 events refer to it by offset) */ };
   std::vector<Job> jobs((size_t)nchunks);
   std::vector<Slot> slots(engs.size());
   for (size_t k = 0; k < engs.size(); ++k) { slots[k].e = engs[k]; slots[k].kept.resize((size_t)step); }
@@ -238,6 +253,7 @@ int main(int argc, char **argv) {
   int next_add = 0;
   std::string fail;
   std::vector<std::string> overflowed;
+  long n_truncated = 0;                            // -V: windows whose trace did not fit the batch's trace_words_for
   // results of a finished run are copied out (the engine's buffers live until its next upload) and added to the
   // VariantDB strictly in chunk order: addVar order is window order
   auto finish = [&](Slot &sl) -> bool {
@@ -266,7 +282,11 @@ int main(int argc, char **argv) {
         const int tw = sl.kept[(size_t)w];
         const char *hdr = lancet_host_window_hdr(H, tw);
         int32_t start = 0, end = 0; lancet_host_window_span(H, tw, &start, &end);
-        char *t = lancet_trace_format(evt + (size_t)w * wpw, elen[w], (int32_t)(sl.base + w + 1), hdr, chr_names[lancet_host_window_chrom(H, tw)], start, end, dfs_limit);
+        const bool l2 = more_verbose && (size_t)w < sl.raw.size();
+        if (l2 && elen[w] == wpw) ++n_truncated;
+        char *t = l2 ? lancet_trace_format2(evt + (size_t)w * wpw, elen[w], wpw, (int32_t)(sl.base + w + 1), hdr, chr_names[lancet_host_window_chrom(H, tw)], start, end, dfs_limit,
+                                            sl.raw[(size_t)w].data(), (uint32_t)sl.raw[(size_t)w].size())
+                     : lancet_trace_format(evt + (size_t)w * wpw, elen[w], (int32_t)(sl.base + w + 1), hdr, chr_names[lancet_host_window_chrom(H, tw)], start, end, dfs_limit);
         if (t) { j.trace += t; lancet_free(t); }
       }
     }
@@ -345,8 +365,20 @@ int main(int argc, char **argv) {
         lancet_window_slice SL;
         if (lancet_host_windows(H, lo, hi, &ho, &SL) != LANCET_OK) return die(lancet_host_last_error(H));
         t_batch += now() - t0; t0 = now();
+        if (more_verbose) {      // (the slice's windows: the batch's are among them)
+          uint32_t longest = 0;
+          for (int32_t i = 0; i < SL.n_windows; ++i) longest = std::max(longest, SL.ref_off[i + 1] - SL.ref_off[i]);
+          if (lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+        }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
         t_engine += now() - t0; t0 = now();
+        if (rc == LANCET_OK && more_verbose) {
+          sl.raw.assign((size_t)nk, std::string());
+          for (int32_t w = 0, i = 0; w < nk; ++w) {
+            while (i < SL.n_windows && SL.widx[i] != sl.kept[(size_t)w]) ++i;
+            if (i < SL.n_windows) sl.raw[(size_t)w].assign(SL.ref_bases + SL.ref_off[i], SL.ref_bases + SL.ref_off[i + 1]);
+          }
+        }
         if (rc == LANCET_OK) { taken = true; if (lancet_host_windows_done(H, lo, hi) != LANCET_OK) return die(lancet_host_last_error(H)); }
         else if (rc == LANCET_NOT_TAKEN) { why = lancet_engine_last_error(sl.e); if (why.compare(0, 11, "not taken: ") == 0) why.erase(0, 11); why = why.substr(0, why.find(':')); }
         else return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
@@ -358,6 +390,12 @@ int main(int argc, char **argv) {
     t_batch += now() - t0;
     if (nk == 0) { jobs[(size_t)c].have = true; if (!flush()) return die(fail); continue; }
     t0 = now();
+    if (!taken && more_verbose) {
+      uint32_t longest = 0;
+      sl.raw.assign((size_t)nk, std::string());
+      for (int32_t w = 0; w < nk; ++w) { longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]); sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
+      if (lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+    }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     t_engine += now() - t0;
     sl.chunk = c; sl.nk = nk; sl.base = done; done += nk; sl.bxn.clear();
@@ -384,6 +422,8 @@ int main(int argc, char **argv) {
     if (ranked) line += " [rank " + std::to_string(rank) + "]";
     fprintf(stderr, "%s\n", line.c_str());
   }
+  if (more_verbose && n_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose -V trace did not fit its buffer (%u paths of the longest window reference + --max-indel-len bases): their text ends with a [trace truncated] line%s\n",
+                                           n_truncated, MV_PATHS, ranked ? (" [rank " + std::to_string(rank) + "]").c_str() : "");
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
   if (ranked) {

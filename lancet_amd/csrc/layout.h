@@ -127,6 +127,7 @@ struct EngineCaps {
   uint32_t bx_cap;       /* barcode ids (u32) of the variants' barcode sets, whole batch (lr_mode)   */
   uint32_t wide_ids;     /* work space laid out for the re-run tier's 64-bit csr words / mate-name records (read ids above 16 bits) */
   uint32_t max_w;        /* longest window reference of the batch, rounded up (>= LC_MAXW_DEFAULT, <= LC_MAXW): sizes the alignment / coverage arrays */
+  uint32_t evt_level;    /* 1 = the reference's -v lines, 2 = its -V (--more-verbose) lines as well (kernels.h EV_REFID ...); 0 with tracing off */
   uint32_t todo_cap;     /* occurrences the mate-overlap prefilter may flag: table_cap in tier 1 (todo[] doubles as the slot -> node table), in the
                             re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
   struct PreLayout pl;   /* hand-off areas of the LDS build kernel (below)                           */

@@ -46,6 +46,8 @@ def lib():
         L.lancet_engine_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float * 2)]
         L.lancet_engine_results_lr.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetVariantLR)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lancet_engine_set_trace.argtypes = [C.c_void_p, C.c_uint32]
+        L.lancet_engine_set_trace_level.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
+        L.lancet_engine_trace_level.argtypes = [C.c_void_p]
         L.lancet_engine_trace.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lancet_engine_rerun_count.argtypes = [C.c_void_p]
         L.lancet_engine_prebuilt_count.argtypes = [C.c_void_p]
@@ -118,7 +120,9 @@ class DeviceReads:
 
 
 class Engine:
-    def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0):
+    def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1):
+        """trace_words: 32-bit words of trace events kept per window (0: no trace).  trace_level 1: the reference's -v lines; 2: its -V
+        (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level)."""
         self.L = lib()
         self.params = params or abi.default_params()
         h = C.c_void_p()
@@ -127,7 +131,11 @@ class Engine:
             raise EngineError(f"lancet_engine_create failed: {ERRORS.get(rc, rc)}")
         self.h = h
         self._batch = None
-        if trace_words:
+        if trace_level not in (1, 2):
+            raise EngineError(f"trace_level {trace_level}: 1 or 2")
+        if trace_words and trace_level == 2:
+            self._chk(self.L.lancet_engine_set_trace_level(self.h, trace_words, 2))
+        elif trace_words:
             self.L.lancet_engine_set_trace(self.h, trace_words)
 
     def _chk(self, rc):
@@ -325,6 +333,8 @@ class Engine:
         return s.value, b.value
 
     def trace_text(self) -> str:
+        """The trace of the last run as the reference prints it: the -v lines, at trace_level 2 the -V lines among them (and, for a window whose
+        events did not fit trace_words, a line that says so)."""
         lp = C.POINTER(C.c_uint32)()
         ep = C.POINTER(C.c_uint32)()
         wpw = C.c_uint32()
@@ -338,7 +348,12 @@ class Engine:
         for w in range(b.n_windows):
             words = ev[w * wpw.value: w * wpw.value + int(lens[w])]
             end = int(b.ref_start[w]) + int(b.ref_off[w + 1] - b.ref_off[w])
-            parts.append(_trace.format_window(words, w + 1, b.hdr[w], b.chrom[w], int(b.ref_start[w]), end, dfs_limit=int(self.params.dfs_limit)))
+            if self.L.lancet_engine_trace_level(self.h) == 2:
+                rawseq = bytes(b.ref_bases[int(b.ref_off[w]):int(b.ref_off[w + 1])]).decode()
+                parts.append(_trace.format_window2(words, wpw.value, w + 1, b.hdr[w], b.chrom[w], int(b.ref_start[w]), end,
+                                                   dfs_limit=int(self.params.dfs_limit), rawseq=rawseq))
+            else:
+                parts.append(_trace.format_window(words, w + 1, b.hdr[w], b.chrom[w], int(b.ref_start[w]), end, dfs_limit=int(self.params.dfs_limit)))
         return "".join(parts)
 
     def phase_times(self):

@@ -8,18 +8,33 @@ from typing import List, Sequence
 (EV_PROCESS, EV_REPEAT_REF, EV_NEAR_REF, EV_READS, EV_STATS, EV_MARKREF, EV_LOWCOV, EV_CLEANDEAD, EV_COMPRESS, EV_CC,
  EV_CCID, EV_CCEND, EV_TRIM, EV_AMBIG_SRC, EV_NOMATCH_SRC, EV_AMBIG_SNK, EV_NOMATCH_SNK, EV_CYCLE, EV_TIPS_ROUND,
  EV_TIPS_REMOVED, EV_LINKS, EV_LOOKREP, EV_MISSING, EV_SEARCH, EV_NEAR_QRY, EV_DFSLIMIT, EV_PATH, EV_TS, EV_PATH_END,
- EV_EKA_END, EV_FOUND, EV_END) = range(1, 33)
+ EV_EKA_END, EV_FOUND, EV_END,
+ # trace level 2 (the reference's -V lines; kernels.h)
+ EV_REFID, EV_RCYC_READ, EV_RCYC, EV_LOOKING, EV_CHK_SRC, EV_RM_SRC, EV_CHK_SNK, EV_RM_SNK, EV_ALN, EV_TRUNC) = range(1, 43)
 
 
 def _bytes(words: Sequence[int], at: int, n: int):
     nwords = ((n + 3) // 4 + 7) // 8 * 8
     raw = b"".join(int(w).to_bytes(4, "little") for w in words[at:at + nwords])
-    return raw[:n].decode(), at + nwords
+    return raw[:n].decode(errors="replace"), at + nwords
 
 
 def format_window(words: Sequence[int], idx1: int, hdr: str, chrom: str, start: int, end: int, dfs_limit: int = 1000000) -> str:
+    return format_window2(words, 0, idx1, hdr, chrom, start, end, dfs_limit=dfs_limit)
+
+
+def format_window2(words: Sequence[int], words_per_window: int, idx1: int, hdr: str, chrom: str, start: int, end: int,
+                   dfs_limit: int = 1000000, rawseq: str = "") -> str:
+    """format_window for a level-2 trace (lancet_engine_set_trace_level): `words` = the window's evt_len words, words_per_window as given
+    to the engine (len(words) == words_per_window marks a window whose events did not fit), rawseq = the window's reference, which the
+    level-2 events refer to by offset.  With level-1 events the text is format_window's."""
     out: List[str] = []
     i = 0
+    truncated = False
+    if words_per_window >= 16 and len(words) == words_per_window and int(words[words_per_window - 8]) == EV_TRUNC:
+        truncated = True
+        words = words[:min(int(words[words_per_window - 7]), words_per_window - 8)]
+    cyc_read = ""
     ccids: List[int] = []
     while i + 8 <= len(words):
         code, a, b, c, d, e, f, g = (int(x) for x in words[i:i + 8])
@@ -84,6 +99,7 @@ def format_window(words: Sequence[int], idx1: int, hdr: str, chrom: str, start: 
             ref, i = _bytes(words, i, b)
             qry, i = _bytes(words, i, b)
             hw = [int(x) for x in words[i:i + 6]]            # 12 x u16: HPRN HPRT HPAN HPAT, each {hp1, hp2, hp0}
+            hw += [0] * (6 - len(hw))                        # (a stream cut off behind the transcript's event: as host_trace.cc reads it)
             i += 8
             h = [(hw[q // 2] >> (16 * (q % 2))) & 0xFFFF for q in range(12)]
             hp = lambda o: f"{h[o + 2]},{h[o]},{h[o + 1]}"     # printed as hp0,hp1,hp2 (reference src/Graph.cc:1138-1141)
@@ -104,4 +120,29 @@ def format_window(words: Sequence[int], idx1: int, hdr: str, chrom: str, start: 
             if c:
                 out.append(" Found cycle in assembly\n")
             out.append("FINISHED\n")
+        elif code == EV_REFID:
+            out.append(f"refid: {a}\n")
+        elif code == EV_RCYC_READ:
+            if c:
+                cyc_read = rawseq[:b]
+            else:
+                cyc_read, i = _bytes(words, i, b)
+        elif code == EV_RCYC:
+            out.append(f"cycle detected in read {a} offset: {b} : {cyc_read}\n")
+        elif code == EV_LOOKING:
+            out.append(f"Looking at {hdr} {b} {rawseq[a:a + b]}\n")
+        elif code == EV_CHK_SRC:
+            out.append("checking for other source edges\n")
+        elif code == EV_CHK_SNK:
+            out.append("checking for other sink edges\n")
+        elif code in (EV_RM_SRC, EV_RM_SNK):
+            nid, i = _bytes(words, i, a)
+            out.append(("  removing node before source: " if code == EV_RM_SRC else "  removing node after sink: ") + nid + "\n")
+        elif code == EV_ALN:
+            p, i = _bytes(words, i, c)
+            out.append(f"alignment\nr:  {rawseq[a:a + b]}\np:  {p}\n")
+    if truncated and out and not out[-1].endswith("\n"):
+        out.append("\n")                                     # (a line of its own, also after a line whose end was cut)
+    if truncated:
+        out.append(f"[trace truncated: window {idx1} needs more than {words_per_window} trace words]\n")
     return "".join(out)
