@@ -1534,6 +1534,30 @@ int lancet_debug_pre_cmp(lancet_engine *e, uint32_t *out) {
   return LANCET_OK;
 }
 
+// test hook: the table order of every graph of window w that the last run left in a hand-off area -- the window's own area, then the pool
+// areas that PreHdr::next chains to it (graphs built ahead, graphs of the build service) -- as host_common.h lc_pre_order_words lays
+// them out, one graph after the other.  Returns the words written (at most `cap`), or an error.  It only reads.
+int lancet_debug_pre_order(lancet_engine *e, int w, uint32_t *out, int cap) {
+  if (!e || !e->uploaded || !e->ran || !e->d_pre.p || w < 0 || w >= e->n_windows) return LANCET_E_STATE;
+  if (e->submitted) { e->err = "hand-off areas read while a batch is in flight"; return LANCET_E_STATE; }
+  HIPCHK(e, hipSetDevice(e->device));
+  const size_t stride = e->caps.pl.stride;
+  std::vector<uint8_t> area(stride);
+  std::vector<uint32_t> words;
+  const uint8_t *src = (const uint8_t *)e->d_pre.p + (size_t)w * stride;
+  for (int hops = 0; hops < 64; ++hops) {
+    HIPCHK(e, lc_copy(e, area.data(), src, stride, hipMemcpyDeviceToHost));
+    const int next = lc_pre_order_words(area.data(), e->caps.pl, &words);
+    if (next < 0) { e->err = "debug_pre_order: an index of the hand-off area lies outside its array"; return LANCET_E_STATE; }
+    if (next == 0) break;
+    if (!e->d_prepool.p || (uint32_t)next > e->pool_cap) { e->err = "debug_pre_order: PreHdr::next outside the pool"; return LANCET_E_STATE; }
+    src = (const uint8_t *)e->d_prepool.p + (size_t)(next - 1) * stride;
+  }
+  if ((size_t)cap < words.size()) return LANCET_E_ARG;
+  memcpy(out, words.data(), 4 * words.size());
+  return (int)words.size();
+}
+
 // graphs the build kernel built ahead (a later k of a window whose first k was going to be rejected) / how many of them the
 // window kernel took
 int lancet_engine_ahead_counts(lancet_engine *e, int32_t *built, int32_t *used) {

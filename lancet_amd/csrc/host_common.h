@@ -65,6 +65,44 @@ static inline PreLayout lc_pre_layout_for_batch(const lancet_window_batch *b, si
   std::vector<uint32_t> wb; return lc_pre_layout_for_sizes(lc_sizes_of_batch(b, &wb), n_areas, budget, force, lr);
 }
 
+// Test hook (engine.hip lancet_debug_pre_order and its twin in tests/emu/emu_engine.cc): what ONE hand-off area -- a host copy of it -- says
+// about the table order, appended to `out`:
+//   K, status, N, nsurv, have_order, ht_bc, ht_next_resize, numcomp, refcomp, big, PreCmp::done, m_live          (12 words)
+//   with have_order, per table position i < nsurv: nhash[order[i]] (low, high word), the comp of that survivor's record
+//   with done, per position i < m_live of CLIVE: the hash of the node there (low, high; a special node's is PreCmp::spec_hash)
+// Returns PreHdr::next (0: the last graph of the window's chain), -1 when an index in the area points outside its array.
+static inline int lc_pre_order_words(const uint8_t *area, const PreLayout &pl, std::vector<uint32_t> *out) {
+  const PreHdr *H = (const PreHdr *)(area + PRE_OFF_HDR);
+  const PreCmp *CH = (const PreCmp *)(area + pl.chdr);
+  const bool built = H->status == PB_BUILT, ord = built && H->have_order == 1u, done = ord && CH->done == 1u;
+  const uint32_t hdr[12] = {(uint32_t)H->K, H->status, built ? H->N : 0u, built ? H->nsurv : 0u, ord ? 1u : 0u, ord ? H->ht_bc : 0u, ord ? H->ht_next_resize : 0u,
+                            ord ? H->numcomp : 0u, ord ? H->refcomp : 0u, built ? H->big : 0u, done ? 1u : 0u, done ? CH->m_live : 0u};
+  out->insert(out->end(), hdr, hdr + 12);
+  if (!ord) return (int)H->next;
+  const unsigned long long *nhash = (const unsigned long long *)(area + pl.nhash);
+  const uint32_t *sid = (const uint32_t *)(area + pl.sid), *order = (const uint32_t *)(area + pl.order), *clive = (const uint32_t *)(area + pl.clive);
+  const NodeGr *pgr = (const NodeGr *)(area + pl.pgr);
+  const uint32_t nsurv = H->nsurv;
+  if (nsurv > PB_SCAP || H->N > pl.ncap) return -1;
+  std::vector<uint32_t> si_of(H->N, LC_NIL);
+  for (uint32_t si = 0; si < nsurv; ++si) { if (sid[si] >= H->N) return -1; si_of[sid[si]] = si; }
+  for (uint32_t i = 0; i < nsurv; ++i) {
+    const uint32_t n = order[i];
+    if (n >= H->N || si_of[n] == LC_NIL) return -1;
+    out->push_back((uint32_t)nhash[n]); out->push_back((uint32_t)(nhash[n] >> 32)); out->push_back((uint32_t)pgr[si_of[n]].comp);
+  }
+  if (!done) return (int)H->next;
+  if (CH->m_live > PB_CMAX + 2u) return -1;
+  for (uint32_t i = 0; i < CH->m_live; ++i) {
+    const uint32_t idx = clive[i];
+    unsigned long long h;
+    if (idx & 0x80000000u) { if ((idx & 0xFFu) > 1u) return -1; h = CH->spec_hash[idx & 0xFFu]; }
+    else { if (idx >= nsurv) return -1; h = nhash[sid[idx]]; }
+    out->push_back((uint32_t)h); out->push_back((uint32_t)(h >> 32));
+  }
+  return (int)H->next;
+}
+
 // Node limit of the re-run tier: `limit` (65 536 unless LANCET_MAX_NODES says otherwise), 2^20 when `grow` and a window has 65 535 reads or more.
 static inline uint32_t lc_tier2_nodes_for_sizes(const LcBatchSizes &b, uint32_t limit, bool grow) {
   if (grow) for (int w = 0; w < b.n_windows; ++w) if (b.read_begin[w + 1] - b.read_begin[w] >= 0xFFFFu) return limit > (1u << 20) ? limit : (1u << 20);

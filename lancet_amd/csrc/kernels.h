@@ -1600,7 +1600,7 @@ DEVNI void build_tables(Ctx &c) {
     // distinct k-mers (previous build of the window + 25 %, else an eighth of the occurrences + the reference's) at a
     // load <= 2/3 instead of the worst case; a table that fills up is doubled and the insert redone (below).
     const uint32_t est = S.N_last ? S.N_last + S.N_last / 4 : o / 8 + (uint32_t)S.reflen;
-    uint32_t tcap = 1024;
+    uint32_t tcap = 1024u < C.table_cap ? 1024u : C.table_cap;      // (a work space of fewer than 512 nodes has fewer slots than that: a batch of a few short reads, LANCET_NODE_CAP1 below 512)
     while (tcap < est + est / 2 && tcap < C.table_cap) tcap <<= 1;
     if (C.table_start) tcap = C.table_start < C.table_cap ? C.table_start : C.table_cap;
     S.tmask = tcap - 1; S.tfull = 0;
@@ -5580,7 +5580,7 @@ DEVNI void load_prebuilt_lr(Ctx &c, LC_GLOBAL const uint8_t *area) {
     else { for (int q = 0; q < 4; ++q) W.refcov[4 * (i + K - 1) + q] = v[q]; for (int q = 0; q < 6; ++q) W.refhp[6 * (i + K - 1) + q] = h[q]; }
   }
   // ---- 6
-  WG_LANE0 { uint32_t tcap = 1024; while (tcap < 2u * nsurv + 2u && tcap < LC_CTX(c).C->table_cap) tcap <<= 1; S.tmask = tcap - 1u; S.tfull = 0; }
+  WG_LANE0 { uint32_t tcap = 1024u < LC_CTX(c).C->table_cap ? 1024u : LC_CTX(c).C->table_cap; while (tcap < 2u * nsurv + 2u && tcap < LC_CTX(c).C->table_cap) tcap <<= 1; S.tmask = tcap - 1u; S.tfull = 0; }
   const uint32_t mask = wg_bcastu(&S.tmask);
   WG_FOR(i, mask + 1u) { lc_u4 z; z.x = 0; z.y = 0; z.z = LC_NIL; z.w = 0; *(lc_u4 *)(W.slots + 4 * (size_t)i) = z; }
   WG_SYNC_FENCE();

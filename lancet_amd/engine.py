@@ -19,6 +19,33 @@ _LIB = None
 ERRORS = {0: "OK", -1: "bad argument", -2: "no HIP device", -3: "HIP error", -4: "unsupported", -5: "out of memory", -6: "bad state"}
 
 
+PRE_ORDER_WORDS = 64 * (12 + 3 * 2048 + 2 * 834)      # room for Engine.pre_order: a chain of 64 graphs at the hand-off limits
+
+
+def parse_pre_order(words):
+    """The words of lancet_debug_pre_order (csrc/host_common.h lc_pre_order_words) as one dict per graph: K, built, N, nsurv, have_order,
+    ht_bc, ht_next_resize, numcomp, refcomp, big, done, m_live; with have_order `hashes` (uint64 per table position) and `comp`; with
+    done `live_hashes` (the table after markRefEnds(1) and compress(1), special nodes included)."""
+    import numpy as np
+    graphs, at = [], 0
+    names = ("K", "status", "N", "nsurv", "have_order", "ht_bc", "ht_next_resize", "numcomp", "refcomp", "big", "done", "m_live")
+    while at < len(words):
+        g = {k: int(v) for k, v in zip(names, words[at:at + 12])}
+        g["built"] = g.pop("status") == 1
+        at += 12
+        if g["have_order"]:
+            rows = np.asarray(words[at:at + 3 * g["nsurv"]], dtype=np.uint64).reshape(g["nsurv"], 3)
+            g["hashes"] = rows[:, 0] | (rows[:, 1] << np.uint64(32))
+            g["comp"] = rows[:, 2].astype(np.int64)
+            at += 3 * g["nsurv"]
+        if g["done"]:
+            rows = np.asarray(words[at:at + 2 * g["m_live"]], dtype=np.uint64).reshape(g["m_live"], 2)
+            g["live_hashes"] = rows[:, 0] | (rows[:, 1] << np.uint64(32))
+            at += 2 * g["m_live"]
+        graphs.append(g)
+    return graphs
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -310,6 +337,17 @@ class Engine:
             return []
         o = out.reshape(-1, 8)[:nw]
         return [dict(built=int(r[0] & 0xFF) == 1, K=int(r[1]), nodes=int(r[3]), order=bool(r[0] >> 16 & 1)) for r in o]
+
+    def pre_order(self, w):
+        """test hook: the table order of every graph of window w that the last run left in a hand-off area -- the window's first graph, then
+        the graphs built ahead and the build service's (PreHdr::next) -- as parse_pre_order returns them"""
+        import numpy as np
+        out = np.zeros(PRE_ORDER_WORDS, dtype=np.uint32)
+        self.L.lancet_debug_pre_order.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = self.L.lancet_debug_pre_order(self.h, int(w), out.ctypes.data, len(out))
+        if n < 0:
+            self._chk(n)
+        return parse_pre_order(out[:n])
 
     def ahead_counts(self):
         """(graphs the build kernel built ahead at a later k, how many the window kernel took)"""

@@ -567,6 +567,28 @@ struct Graph {
   bool align_undefined = false;                                                      // processPath met a pair the reference's traceback walks out of (global_align_aff)
   uint64_t n_kmers = 0; uint32_t max_nodes = 0, sum_nodes = 0; int n_builds = 0;
   std::unordered_map<std::string, std::set<uint32_t>> bxT, bxN;                       // Graph_t::bx_table_tmr / _nml
+  // Opt-in (lancet_oracle_run's verbose bit 1), read only: what the node table looks like from outside at four points of every graph --
+  // records of 64-bit words [tag, window, k, words that follow, ...]:
+  //   1 after buildgraph:                                  nodes.size(), bucket_count()
+  //   2 after removeLowCov(false, 0) + markConnectedComponents:  allcomp, refcomp, bucket_count(), n, then per node in iteration order
+  //                                                         std::hash of its key, comp, touchRef
+  //   3 after markRefEnds(1):                              bucket_count(), n, then the keys' hashes in iteration order
+  //   4 after compress(1):                                 bucket_count(), n, then the keys' hashes in iteration order
+  std::vector<uint64_t> *order_dump = nullptr;
+  void dumpTable(int tag) {
+    if (!order_dump) return;
+    std::vector<uint64_t> &d = *order_dump;
+    d.push_back((uint64_t)tag); d.push_back((uint64_t)cur_window); d.push_back((uint64_t)K);
+    const size_t at = d.size(); d.push_back(0);
+    if (tag == 1) d.push_back(nodes.size());
+    if (tag == 2) { d.push_back((uint64_t)ref->allcomp); d.push_back((uint64_t)ref->refcomp); }
+    d.push_back(nodes.bucket_count());
+    if (tag != 1) {
+      d.push_back(nodes.size());
+      for (auto &kv : nodes) { d.push_back(nodes.hash_function()(kv.first)); if (tag == 2) { d.push_back((uint64_t)kv.second->comp); d.push_back(kv.second->touchRef ? 1 : 0); } }
+    }
+    d[at] = d.size() - at - 1;
+  }
 
   void setK(int k) { K = k; MAX_LINK_LEN = (int)floor((double)K / 2.0); }              // Graph.hh:143
   void clear(bool flag) {                                                            // Graph.cc:29-60
@@ -1240,6 +1262,7 @@ int processGraph(Graph &g, RefInfo *refinfo, int graphCnt, lancet_window_stats *
     if (isRepeat(refinfo->rawseq, k)) { if (g.verbose) tr << "Repeat in reference sequence for kmer " << k << std::endl; rptInRef = true; continue; }
     if (isAlmostRepeat(refinfo->rawseq, k, P->max_mismatch)) { if (g.verbose) tr << "Near-perfect repeat in reference sequence for kmer " << k << std::endl; rptInRef = true; continue; }
     g.buildgraph(refinfo);
+    g.dumpTable(1);
     st->final_k = k;
     double avgcov = ((double)g.totalreadbp) / ((double)refinfo->rawseq.length());
     if (g.verbose) {
@@ -1249,11 +1272,14 @@ int processGraph(Graph &g, RefInfo *refinfo, int graphCnt, lancet_window_stats *
     g.markRefNodes();
     g.removeLowCov(false, 0);
     int numcomp = g.markConnectedComponents();
+    g.dumpTable(2);
     for (int c = 1; c <= numcomp; ++c) {
       if (g.verbose) g.printStats(c);
       g.markRefEnds(c);
+      if (c == 1) g.dumpTable(3);
       if (g.hasCycle()) { g.clear(false); cycleInGraph = true; break; }
       g.compress(c);
+      if (c == 1) g.dumpTable(4);
       if (g.verbose) g.printStats(c);
       g.removeLowCov(true, c);
       g.removeTips(c);
@@ -1284,6 +1310,7 @@ struct OracleResult {
   std::string blob;
   std::vector<lancet_window_stats> stats;
   std::string trace;
+  std::vector<uint64_t> order_dump;
 };
 
 }  // namespace
@@ -1291,7 +1318,8 @@ struct OracleResult {
 extern "C" {
 
 // Runs the restated hot path over a batch.  chr_names (optional) are only used for the trace text.
-// Returns an opaque handle; accessors below.  verbose!=0 fills the trace (reference `-v` stderr subset).
+// Returns an opaque handle; accessors below.  verbose bit 0 fills the trace (reference `-v` stderr subset), bit 1 the table dump
+// (Graph::dumpTable; lancet_oracle_order_dump).
 void *lancet_oracle_run(const lancet_params *P, const lancet_window_batch *b, const char *const *chr_names,
                         const char *const *hdrs, int verbose) {
   auto *res = new OracleResult();
@@ -1300,7 +1328,8 @@ void *lancet_oracle_run(const lancet_params *P, const lancet_window_batch *b, co
   tr.precision(1);
   std::vector<OutVariant> out;
   Graph g;
-  g.P = P; g.verbose = verbose != 0; g.tr = &tr; g.out = &out;
+  g.P = P; g.verbose = (verbose & 1) != 0; g.tr = &tr; g.out = &out;
+  if (verbose & 2) g.order_dump = &res->order_dump;
   res->stats.resize(b->n_windows);
   int graphCnt = 0;
   for (int w = 0; w < b->n_windows; ++w) {
@@ -1358,6 +1387,7 @@ uint32_t lancet_oracle_bx_blob_len(void *h) { return ((OracleResult *)h)->bx_blo
 uint32_t lancet_oracle_blob_len(void *h) { return ((OracleResult *)h)->blob.size(); }
 const lancet_window_stats *lancet_oracle_stats(void *h) { return ((OracleResult *)h)->stats.data(); }
 const char *lancet_oracle_trace(void *h) { return ((OracleResult *)h)->trace.c_str(); }
+const uint64_t *lancet_oracle_order_dump(void *h, uint64_t *n_words) { *n_words = ((OracleResult *)h)->order_dump.size(); return ((OracleResult *)h)->order_dump.data(); }
 void lancet_oracle_free(void *h) { delete (OracleResult *)h; }
 
 // Stand-alone pieces, exported so tests can pin kernels individually.

@@ -45,6 +45,8 @@ def lib():
         L.lancet_oracle_stats.argtypes = [C.c_void_p]
         L.lancet_oracle_trace.restype = C.c_char_p
         L.lancet_oracle_trace.argtypes = [C.c_void_p]
+        L.lancet_oracle_order_dump.restype = C.POINTER(C.c_uint64)
+        L.lancet_oracle_order_dump.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.lancet_oracle_free.argtypes = [C.c_void_p]
         L.lancet_oracle_align.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
         L.lancet_oracle_std_hash.restype = C.c_uint64
@@ -55,8 +57,13 @@ def lib():
     return _LIB
 
 
-def run(batch, params=None, verbose: bool = False):
-    """Returns (variants [dict], stats [dict], trace str)."""
+def run(batch, params=None, verbose: bool = False, order_dump: bool = False):
+    """Returns (variants [dict], stats [dict], trace str); with order_dump a fourth element: what the node table of every graph looked
+    like from outside (lancet_oracle.cc Graph::dumpTable), {(window, k): dict} with
+      N, buckets_built                                      after buildgraph
+      hashes, comp, touch_ref, allcomp, refcomp, buckets    after removeLowCov(false, 0) + markConnectedComponents, in iteration order
+      buckets_ends, hashes_ends                             after markRefEnds(1)   (absent without a component)
+      buckets_compressed, hashes_compressed                 after compress(1)      (absent when hasCycle gave the graph up before)"""
     L = lib()
     p = params or abi.default_params()
     cb = abi.batch_to_c(batch)
@@ -67,7 +74,7 @@ def run(batch, params=None, verbose: bool = False):
     names = [id2chr.get(i, str(i)) for i in range(max(id2chr) + 1)] if id2chr else []
     cn = abi.c_string_array(names)
     hd = abi.c_string_array(batch.hdr)
-    h = L.lancet_oracle_run(C.byref(p), C.byref(cb), cn, hd, 1 if verbose else 0)
+    h = L.lancet_oracle_run(C.byref(p), C.byref(cb), cn, hd, (1 if verbose else 0) | (2 if order_dump else 0))
     try:
         n = L.lancet_oracle_n_variants(h)
         blob = C.string_at(L.lancet_oracle_blob(h), L.lancet_oracle_blob_len(h)) if L.lancet_oracle_blob_len(h) else b""
@@ -78,9 +85,35 @@ def run(batch, params=None, verbose: bool = False):
         stats = [dict(status=sp[i].status, final_k=sp[i].final_k, n_builds=sp[i].n_builds, n_variants=sp[i].n_variants,
                       n_kmers=sp[i].n_kmers, max_nodes=sp[i].max_nodes, sum_nodes=sp[i].sum_nodes) for i in range(batch.n_windows)]
         trace = L.lancet_oracle_trace(h).decode()
+        dump = _parse_order_dump(L, h) if order_dump else None
     finally:
         L.lancet_oracle_free(h)
-    return variants, stats, trace
+    return (variants, stats, trace, dump) if order_dump else (variants, stats, trace)
+
+
+def _parse_order_dump(L, h):
+    import numpy as np
+    n = C.c_uint64()
+    p = L.lancet_oracle_order_dump(h, C.byref(n))
+    d = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint64)
+    graphs, at = {}, 0
+    while at < len(d):
+        tag, w, k, cnt = (int(x) for x in d[at:at + 4])
+        body = d[at + 4:at + 4 + cnt]
+        g = graphs.setdefault((w, k), {})
+        if tag == 1:
+            g.clear()                                      # (never twice per window and k; a clean start all the same)
+            g["N"], g["buckets_built"] = int(body[0]), int(body[1])
+        elif tag == 2:
+            g["allcomp"], g["refcomp"], g["buckets"] = int(body[0]), int(body[1]), int(body[2])
+            rows = body[4:].reshape(int(body[3]), 3)
+            g["hashes"], g["comp"], g["touch_ref"] = rows[:, 0].copy(), rows[:, 1].astype(np.int64), rows[:, 2].astype(bool)
+        else:
+            name = "ends" if tag == 3 else "compressed"
+            g["buckets_" + name] = int(body[0])
+            g["hashes_" + name] = body[2:2 + int(body[1])].copy()
+        at += 4 + cnt
+    return graphs
 
 
 def align(S: str, T: str):

@@ -51,9 +51,10 @@ LAST_AHEAD = [0, 0]          # graphs built ahead at a later k / taken by the wi
 LAST_PREBUILT = [0]          # windows of the last run whose first graph came from the LDS build kernel
 LAST_CMP = [0]               # windows of the last run whose first compress (and markRefEnds) the build kernel did
 LAST_SVC = [0, 0, 0]         # build service, last run: requests posted by suspended windows / served in LDS / taken back (general build)
+LAST_PRE_ORDER = []          # run(..., pre_order=True): per window the graphs its hand-off areas hold (lancet_amd.engine.parse_pre_order)
 
 
-def run(batch, params=None, evt_cap: int = 0):
+def run(batch, params=None, evt_cap: int = 0, pre_order: bool = False):
     """Returns (variants sorted by (window, seq), stats, trace text)."""
     L = lib()
     p = params or abi.default_params()
@@ -66,6 +67,13 @@ def run(batch, params=None, evt_cap: int = 0):
         LAST_AHEAD[0], LAST_AHEAD[1] = int(L.lancet_emu_n_ahead_built(h)), int(L.lancet_emu_n_ahead_used(h))
         LAST_CMP[0] = int(L.lancet_emu_n_cmp_done(h))
         LAST_SVC[0], LAST_SVC[1], LAST_SVC[2] = int(L.lancet_emu_n_svc_posted(h)), int(L.lancet_emu_n_svc_built(h)), int(L.lancet_emu_n_svc_stolen(h))
+        LAST_PRE_ORDER.clear()
+        if pre_order:
+            from lancet_amd import engine as _engine
+            buf = np.zeros(_engine.PRE_ORDER_WORDS, np.uint32)
+            for w in range(batch.n_windows):
+                nw = int(L.lancet_emu_pre_order(C.c_void_p(h), w, buf.ctypes.data_as(C.c_void_p), len(buf)))
+                LAST_PRE_ORDER.append(_engine.parse_pre_order(buf[:nw]) if nw >= 0 else [])
         bl = L.lancet_emu_blob_len(h)
         blob = C.string_at(L.lancet_emu_blob(h), bl) if bl else b""
         variants = abi.variants_to_py(L.lancet_emu_variants(h), n, blob)

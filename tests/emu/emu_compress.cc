@@ -5,8 +5,10 @@
 // (reference src/Graph.cc:2486-2762) -- compress (the literal loop), compress_prepare -> compress_fast (record replay), compress_prepare ->
 // compress_rank (pointer jumping over ports) and compress_wg (the whole-wave loop; its one-lane form in the FAT build) -- each from the
 // same start state, next to a plain model of the reference lines (strings, per-position coverage entries, edge vectors) that shares no
-// code with them.  The build kernel's bl_compress_first needs a whole hand-off area and is held where it can be observed, by the counts of
-// test_emu_kernels.py.
+// code with them.  The build kernel's bl_compress_first needs a whole hand-off area and is held where it can be observed: by the counts of
+// test_emu_kernels.py, and -- the table it leaves, position by position -- by test_table_order_windows_emu.py, which reads CLIVE back
+// (lancet_debug_pre_order) and holds it against the oracle's unordered_map after compress(1).  The build kernel's tail in front of it
+// (table order, cleanDead, components) has a rig of its own: emu_table_order.cc for the rules, table_order_cases.py for whole windows.
 #define LANCET_WAVE_EMU 1
 #include <algorithm>
 #include <cstdio>

@@ -24,10 +24,12 @@ struct EmuResult {
   uint32_t n_prebuilt, n_ahead_built, n_ahead_used, n_biglist;
   uint32_t n_svc_built, n_svc_stolen, n_svc_posted;
   uint32_t n_cmp_done = 0;
+  std::vector<uint8_t> pre, pool; PreLayout pl; uint32_t pool_cap = 0;      // the hand-off areas as the run left them (lancet_emu_pre_order)
 };
 
 extern "C" void *lancet_emu_run(const lancet_params *P, const lancet_window_batch *b, uint32_t evt_cap) {
-  EngineCaps C = getenv("LANCET_EMU_TIER1") ? lc_caps_for_batch(b, P, evt_cap, 16384, 1)      // (the engine's tier-1 work space: to see which limit a window hits there)
+  // (the engine's tier-1 work space: to see which limit a window hits there; a value above 1 is the node limit, as LANCET_NODE_CAP1 is the engine's)
+  EngineCaps C = getenv("LANCET_EMU_TIER1") ? lc_caps_for_batch(b, P, evt_cap, atoi(getenv("LANCET_EMU_TIER1")) > 1 ? (uint32_t)atoi(getenv("LANCET_EMU_TIER1")) : 16384u, 1)
                                             : lc_caps_for_batch(b, P, evt_cap, lc_tier2_nodes_for_batch(b, 65536, true));      // (the engine's re-run tier, engine.hip lc_upload)
   C.pl = lc_pre_layout_for_batch(b, 1, (size_t)1 << 40, getenv("LANCET_PRE_WIDE") ? atoi(getenv("LANCET_PRE_WIDE")) : -1, P->lr_mode != 0);      // (engine.hip lc_upload)
   C.wide_ids = LC_WIDE_IDS;                        // (libemu_fat.so: the re-run tier's 64-bit csr words, as engine.hip lays its tier 2 out)
@@ -120,7 +122,25 @@ extern "C" void *lancet_emu_run(const lancet_params *P, const lancet_window_batc
   res->n_svc_built = sv.n_built; res->n_svc_stolen = sv.n_stolen; res->n_svc_posted = sv.req_alloc < sv.cap ? sv.req_alloc : sv.cap;
   if (getenv("LANCET_EMU_SVC")) fprintf(stderr, "[emu] svc posted %u built %u failed %u stolen %u\n", sv.req_alloc, sv.n_built, sv.n_failed, sv.n_stolen);
   res->n_variants = nv < C.var_cap ? nv : C.var_cap; res->n_blob = nb;
+  res->pl = C.pl; res->pool_cap = pool_cap; res->pre.swap(pre); res->pool.swap(pool);
   return res;
+}
+// the twin of engine.hip lancet_debug_pre_order: the table order of every graph of window w that the run left in a hand-off area
+extern "C" int lancet_emu_pre_order(void *h, int w, uint32_t *out, int cap) {
+  const EmuResult *r = (const EmuResult *)h;
+  if (r->pre.empty() || w < 0 || (size_t)(w + 1) * r->pl.stride > r->pre.size()) return -6;
+  std::vector<uint32_t> words;
+  const uint8_t *src = r->pre.data() + (size_t)w * r->pl.stride;
+  for (int hops = 0; hops < 64; ++hops) {
+    const int next = lc_pre_order_words(src, r->pl, &words);
+    if (next < 0) return -6;
+    if (next == 0) break;
+    if ((uint32_t)next > r->pool_cap) return -6;
+    src = r->pool.data() + (size_t)(next - 1) * r->pl.stride;
+  }
+  if ((size_t)cap < words.size()) return -1;
+  memcpy(out, words.data(), 4 * words.size());
+  return (int)words.size();
 }
 extern "C" uint32_t lancet_emu_n_variants(void *h) { return ((EmuResult *)h)->n_variants; }
 extern "C" const lancet_variant *lancet_emu_variants(void *h) { return ((EmuResult *)h)->variants.data(); }
