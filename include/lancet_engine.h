@@ -313,6 +313,39 @@ int lancet_engine_results(lancet_engine *e, const lancet_variant **variants, uin
 /* Linked-read annotations of the last run (lr_mode engines; otherwise *lr = NULL): lr[i] belongs to variants[i]. */
 int lancet_engine_results_lr(lancet_engine *e, const lancet_variant_lr **lr, const uint32_t **bx_blob, uint32_t *bx_blob_len);
 int lancet_engine_last_timing(lancet_engine *e, float out[2]);
+
+/* ---- assembled haplotypes ----
+ * One lancet_haplotype per path the window kernel compared with the window reference (the reference's Graph_t::processPath, the calls for
+ * which its -V prints "alignment" / "r:" / "p:"), in that order.  Off by default; on, it is a result like the records: every build route
+ * (LDS build kernel, graphs built ahead, build service, general build), both tiers, lr_mode and kmer_recovery, with or without a trace.
+ * lancet_engine_set_haplotypes: before an upload, reserve words_per_window 32-bit words per window (0 = off).  A haplotype of len bases
+ * takes LANCET_HAP_HEADER_WORDS + (len + 15) / 16 of them; a value that does not hold one header and one word is LANCET_E_ARG.
+ * LANCET_E_STATE between an upload and its run (the buffers are laid out by the upload) and while a batch is in flight.
+ * A window whose haplotypes do not fit is marked truncated[w] = 1: it keeps, whole, the ones in front of the first that did not fit, and
+ * nothing else about it changes -- the capture never overflows a window and never changes a record, a statistic or a trace word.  A
+ * window with status < 0 has none; a window re-run by the second tier reports that tier's, once.
+ * lancet_engine_results_haplotypes: after a run, ordered by (window, index_in_window); n = 0 and truncated all zero with the capture
+ * off.  Base j of haplotype i: (words[h[i].word_off + j / 16] >> (2 * (j % 16))) & 3, A C G T = 0..3; the bits above len are 0. */
+#define LANCET_HAP_HEADER_WORDS 8
+#define LANCET_HAP_UNALIGNED 1u   /* flags: compared without alignment (same length, few mismatches: the Hamming short-cut, src/Graph.cc:818-826) */
+#define LANCET_HAP_IS_REF 2u      /* flags: identical to the reference stretch                                                         */
+typedef struct lancet_haplotype {
+  int32_t  window;            /* index in the batch */
+  int32_t  index_in_window;   /* 0, 1, 2 ... in processPath order (across components and k, as -V prints them) */
+  uint16_t kmer, component;
+  uint32_t ref_off, ref_len;  /* the stretch of the window reference it was compared with (Ref_t::seq: trim5, length) = the r: line */
+  uint32_t len;               /* bases of the path string = the p: line */
+  uint32_t word_off;          /* (len + 15) / 16 words of `words` from here */
+  int32_t  first_variant, n_variants;   /* seq_in_window of the lancet_variant records this path emitted */
+  uint32_t flags;             /* LANCET_HAP_* ; other bits 0 */
+} lancet_haplotype;
+int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window);
+int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **h, uint32_t *n, const uint32_t **words,
+                                     uint32_t *n_words, const uint8_t **truncated /* [n_windows] */);
+/* Milliseconds on the host clock that the last run's read-back of the haplotypes took (the windows' lengths, the gather of the used words
+ * on the device, one copy, the records); 0 with the capture off. */
+float lancet_engine_haplotype_readback_ms(const lancet_engine *e);
+
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */
 const char *lancet_engine_kernel_name(int i);

@@ -92,6 +92,33 @@ class LancetVariant(C.Structure):
     ]
 
 
+class LancetHaplotype(C.Structure):
+    """lancet_haplotype: one path the window kernel compared with the window reference (lancet_engine_results_haplotypes)."""
+    _fields_ = [("window", C.c_int32), ("index_in_window", C.c_int32), ("kmer", C.c_uint16), ("component", C.c_uint16),
+                ("ref_off", C.c_uint32), ("ref_len", C.c_uint32), ("len", C.c_uint32), ("word_off", C.c_uint32),
+                ("first_variant", C.c_int32), ("n_variants", C.c_int32), ("flags", C.c_uint32)]
+
+
+HAP_HEADER_WORDS = 8          # LANCET_HAP_HEADER_WORDS: a haplotype of n bases takes this + (n + 15) // 16 words of its window's buffer
+HAP_UNALIGNED, HAP_IS_REF = 1, 2
+
+
+def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:
+    """lancet_haplotype records as dicts, `seq` = the path string (2 bits per base, first base in the low bits of a word)."""
+    out = []
+    for i in range(n):
+        h = hptr[i]
+        nw = (h.len + 15) // 16
+        w = words[h.word_off:h.word_off + nw].astype(np.uint32)
+        codes = ((w[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]) & 3).reshape(-1)
+        out.append(dict(window=h.window, index=h.index_in_window, kmer=h.kmer, component=h.component, ref_off=h.ref_off, ref_len=h.ref_len,
+                        len=h.len, first_variant=h.first_variant, n_variants=h.n_variants, flags=h.flags,
+                        seq="".join("ACGT"[c] for c in codes[:h.len]), n_words=int(len(w)),
+                        # the bits of the last word above the last base (0 by contract)
+                        pad_bits=int(w[-1] >> np.uint32(2 * (h.len % 16))) if len(w) and h.len % 16 else 0))
+    return out
+
+
 class LancetWindowStats(C.Structure):
     _fields_ = [("status", C.c_int32), ("final_k", C.c_int32), ("n_builds", C.c_int32), ("n_variants", C.c_int32),
                 ("n_kmers", C.c_uint64), ("max_nodes", C.c_uint32), ("sum_nodes", C.c_uint32)]

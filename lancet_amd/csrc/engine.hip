@@ -217,6 +217,18 @@ __global__ void ref_code_kernel(const char *ref, uint8_t *codes, uint32_t n) {
   if (i < n) codes[i] = (uint8_t)base_code(ref[i]);
 }
 
+// Haplotype capture, read-back: the used words of every window's buffer (`cap` words apart in src) one behind the other in dst -- window w's
+// off[w + 1] - off[w] words at off[w].  One workgroup per window; the host made `off` from the length words, none above cap.
+__global__ void __launch_bounds__(64) hap_compact_kernel(const uint32_t *src, uint32_t cap, const uint32_t *off, uint32_t *dst, int n_windows) {
+  const int w = (int)blockIdx.x;
+  if (w >= n_windows) return;
+  const uint32_t o = off[w];
+  uint32_t n = off[w + 1] - o;
+  if (n > cap) n = cap;
+  const uint32_t *s = src + (size_t)w * cap;
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[o + i] = s[i];
+}
+
 struct DevBuf {
   void *p = nullptr; size_t cap = 0;
   int ensure(size_t n) {
@@ -313,6 +325,12 @@ struct lancet_engine {
   uint32_t evt_cap = 0;
   uint32_t evt_level = 1;     // lancet_engine_set_trace_level: 2 = the -V lines too, every graph through the general build (prebuild / svc off while it is set)
   bool lvl_saved = false, prebuild_cfg = true, svc_cfg = true;   // ... what prebuild / svc were before level 2 switched them off
+  // haplotype capture (lancet_engine_set_haplotypes): words per window of the next upload (0 = off; EngineCaps::hap_cap is what the uploaded batch has),
+  // the windows' length words and buffers, the prefix sums and the dense copy of the read-back, the last run's result and what its read-back took
+  uint32_t hap_words = 0;
+  DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
+  LcHapResult hap;
+  float ms_hap = 0;
   size_t mem_budget = (size_t)96 << 30;
   int max_slots = 5120;      // work-space slots = resident single-wave workgroups: 5 per SIMD (96 VGPRs, < 8 KB LDS each) x 4 SIMDs x CUs
   uint32_t max_nodes_limit = 65536; bool max_nodes_env = false;
@@ -467,7 +485,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   DevBuf *all[] = {&e->d_params, &e->d_batch, &e->d_caps, &e->d_out, &e->d_works, &e->d_chr, &e->d_refstart, &e->d_refoff, &e->d_refasc,
                    &e->d_refcodes, &e->d_readbegin, &e->d_seqoff, &e->d_seq, &e->d_qual, &e->d_label, &e->d_strand, &e->d_mate, &e->d_mapped,
                    &e->d_rinfo, &e->d_name, &e->d_bw, &e->d_gw, &e->d_bases, &e->d_good, &e->d_variants, &e->d_blob, &e->d_counters,
-                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum};
+                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum, &e->d_haplen, &e->d_hap, &e->d_hapoff, &e->d_hapdense};
   for (DevBuf *b : all) b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->evb0) (void)hipEventDestroy(e->evb0);
@@ -501,6 +519,19 @@ int lancet_engine_set_trace_level(lancet_engine *e, uint32_t words_per_window, i
   const bool l2 = level == 2 && words_per_window != 0;
   e->evt_cap = words_per_window; e->evt_level = l2 ? 2u : 1u;
   e->prebuild = l2 ? false : e->prebuild_cfg; e->svc = l2 ? false : e->svc_cfg;
+  return LANCET_OK;
+}
+
+// Haplotype capture: words per window of the uploads that follow.  The buffers and EngineCaps::hap_cap are laid out by an upload, so between an
+// upload and its run the setting cannot change.
+int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotypes while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotypes between an upload and its run"; return LANCET_E_STATE; }
+  if (words_per_window && words_per_window < LC_HAP_MIN_WORDS) {
+    e->err = "set_haplotypes: a window's buffer holds at least one header and one word of bases (" + std::to_string(LC_HAP_MIN_WORDS) + " words)"; return LANCET_E_ARG; }
+  if (words_per_window >= HP_TRUNC) { e->err = "set_haplotypes: words_per_window is below 2^31"; return LANCET_E_ARG; }
+  e->hap_words = words_per_window;
   return LANCET_OK;
 }
 
@@ -577,6 +608,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
     }
   }
   e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
+  e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
 }
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk) {
   if (!e || !b || b->n_windows < 0) return LANCET_E_ARG;
@@ -816,6 +848,13 @@ static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatc
   o.n_bx = (LC_GLOBAL uint32_t *)e->d_counters.p + 3; o.variants_lr = (LC_GLOBAL lancet_variant_lr *)e->d_varlr.p; o.bx_blob = (LC_GLOBAL uint32_t *)e->d_bxblob.p;
   o.stats = (LC_GLOBAL lancet_window_stats *)e->d_stats.p; o.evt_len = (LC_GLOBAL uint32_t *)e->d_evtlen.p; o.evt_out = (LC_GLOBAL uint32_t *)e->d_evt.p; o.phase = e->phase_times ? (LC_GLOBAL unsigned long long *)e->d_phase.p : nullptr; o.win_list = nullptr; o.n_list = 0;
   o.pre = nullptr; o.pre_pool = nullptr; o.n_ahead_used = nullptr; o.skip = nullptr; o.svc = nullptr;
+  o.hap_len = nullptr; o.hap_out = nullptr;
+  if (e->caps.hap_cap) {        // haplotype capture: a buffer per window (both tiers write the same ones); only the length words are cleared
+    ENS(e->d_haplen, sizeof(uint32_t) * (size_t)nw);
+    ENS(e->d_hap, sizeof(uint32_t) * (size_t)nw * e->caps.hap_cap);
+    if (nw) HIPCHK(e, hipMemsetAsync(e->d_haplen.p, 0, sizeof(uint32_t) * (size_t)nw, e->stream));
+    o.hap_len = (LC_GLOBAL uint32_t *)e->d_haplen.p; o.hap_out = (LC_GLOBAL uint32_t *)e->d_hap.p;
+  }
   e->svc_cap = 0;
   e->pred.clear(); e->is_pred.assign(nw, 0);
   if (!e->debug_stop && !e->no_fat && !e->no_early_rerun) {
@@ -1204,6 +1243,7 @@ int lancet_engine_submit(lancet_engine *e) {
   HIPCHK(e, hipSetDevice(e->device));
   e->ran = false;
   e->variants.clear(); e->blob.clear(); e->stats.clear(); e->evt_len.clear(); e->evt.clear(); e->variants_lr.clear(); e->bx_blob.clear();
+  e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1252,6 +1292,29 @@ int lancet_engine_submit(lancet_engine *e) {
   if (rc) { (void)hipStreamSynchronize(e->stream); if (e->stream2) (void)hipStreamSynchronize(e->stream2); e->fat_inflight = false; return rc; }
   HIPCHK(e, hipEventRecord(e->ev_done, e->stream));             // the batch's kernels (build, window, the service's leave signal) are behind this
   e->submitted = true;
+  return LANCET_OK;
+}
+
+// Read-back of the haplotype capture: the windows' length words, then only the words they count -- hap_compact_kernel gathers them into one
+// dense array (window w's at the prefix sum of the lengths before it), which comes over in one copy.  A window without a result has none.
+static int lc_read_haplotypes(lancet_engine *e) {
+  const int nw = e->n_windows;
+  const uint32_t cap = e->caps.hap_cap;
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> len((size_t)nw), off((size_t)nw + 1, 0);
+  HIPCHK(e, lc_copy(e, len.data(), e->d_haplen.p, sizeof(uint32_t) * (size_t)nw, hipMemcpyDeviceToHost));
+  uint64_t total = 0;
+  for (int w = 0; w < nw; ++w) { total += lc_hap_used(len[(size_t)w], cap, e->stats[(size_t)w].status); if (total >= 0xFFFFFFFFull) { e->err = "haplotypes: more than 2^32 words in one batch"; return LANCET_E_OOM; } off[(size_t)w + 1] = (uint32_t)total; }
+  std::vector<uint32_t> dense((size_t)total + 1, 0);
+  if (total) {
+    if (e->d_hapoff.ensure(sizeof(uint32_t) * ((size_t)nw + 1)) || e->d_hapdense.ensure(sizeof(uint32_t) * (size_t)total)) { e->err = "hipMalloc failed (haplotypes)"; return LANCET_E_OOM; }
+    HIPCHK(e, hipMemcpyAsync(e->d_hapoff.p, off.data(), sizeof(uint32_t) * ((size_t)nw + 1), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(hap_compact_kernel, dim3((unsigned)nw), dim3(64), 0, e->stream, (const uint32_t *)e->d_hap.p, cap, (const uint32_t *)e->d_hapoff.p, (uint32_t *)e->d_hapdense.p, nw);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, lc_copy(e, dense.data(), e->d_hapdense.p, sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost));
+  }
+  lc_hap_collect(nw, len.data(), off.data(), dense.data(), e->stats.data(), &e->hap);
+  e->ms_hap = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return LANCET_OK;
 }
 
@@ -1373,6 +1436,7 @@ int lancet_engine_wait(lancet_engine *e) {
     }
     e->variants.erase(std::remove_if(e->variants.begin(), e->variants.end(), [&](const lancet_variant &v) { return e->stats[v.window].status < 0; }), e->variants.end());
   }
+  if (e->caps.hap_cap) { const int rc = lc_read_haplotypes(e); if (rc) return rc; }
   e->ran = true;
   return LANCET_OK;
 }
@@ -1409,6 +1473,20 @@ int lancet_engine_results_lr(lancet_engine *e, const lancet_variant_lr **lr, con
   if (bx_blob_len) *bx_blob_len = (uint32_t)e->bx_blob.size();
   return LANCET_OK;
 }
+
+int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **h, uint32_t *n, const uint32_t **words, uint32_t *n_words, const uint8_t **truncated) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  if (e->hap.truncated.size() != (size_t)std::max(0, e->n_windows)) e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0);
+  if (h) *h = e->hap.h.data();
+  if (n) *n = (uint32_t)e->hap.h.size();
+  if (words) *words = e->hap.words.data();
+  if (n_words) *n_words = (uint32_t)e->hap.words.size();
+  if (truncated) *truncated = e->hap.truncated.data();
+  return LANCET_OK;
+}
+// milliseconds the last run's read-back of the haplotypes took on the host clock (lengths, compaction, copy, parsing); 0 with the capture off
+float lancet_engine_haplotype_readback_ms(const lancet_engine *e) { return e ? e->ms_hap : 0.f; }
 
 int lancet_engine_last_timing(lancet_engine *e, float out[2]) {
   if (!e || !e->ran) return LANCET_E_STATE;

@@ -178,7 +178,42 @@ static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_
   c.lr_mode = p->lr_mode ? 1u : 0u;
   c.bx_cap = c.lr_mode ? (uint32_t)b->n_windows * 8192u + (1u << 20) : 0u;
   c.pl = lc_pre_layout(PB_NCAP, PB_QVCAP, 1u, c.max_w);      // (the engine replaces it per upload: lc_pre_layout_for_batch)
+#ifdef LANCET_WAVE_EMU
+  c.hap_cap = lc_emu_hap_sink.cap;                            // (the engine sets it from lancet_engine_set_haplotypes)
+#endif
   return c;
+}
+
+// ---- haplotype capture (layout.h HP_*): what the window kernels left in the windows' buffers, as lancet_engine_results_haplotypes returns it.
+// Smallest buffer lancet_engine_set_haplotypes accepts: one header and one word of bases.
+#define LC_HAP_MIN_WORDS (HP_HDR + 1u)
+// Words of window w that hold closed entries, from its length word: none for a window that reports no result (status < 0).
+static inline uint32_t lc_hap_used(uint32_t len_word, uint32_t cap, int32_t status) {
+  const uint32_t u = len_word & ~HP_TRUNC;
+  return status < 0 ? 0u : (u < cap ? u : cap);
+}
+struct LcHapResult { std::vector<lancet_haplotype> h; std::vector<uint32_t> words; std::vector<uint8_t> truncated; };
+// len_word[w]: DevOut::hap_len as the run left it; dense: the used words of the windows one behind the other (window w's start at off[w],
+// off[w + 1] - off[w] == lc_hap_used of it).
+static inline void lc_hap_collect(int n_windows, const uint32_t *len_word, const uint32_t *off, const uint32_t *dense, const lancet_window_stats *stats, LcHapResult *r) {
+  r->h.clear(); r->words.clear(); r->truncated.assign((size_t)(n_windows > 0 ? n_windows : 0), 0);
+  for (int w = 0; w < n_windows; ++w) {
+    if (stats[w].status < 0) continue;
+    r->truncated[(size_t)w] = (len_word[w] & HP_TRUNC) ? 1 : 0;
+    const uint32_t *p = dense + off[w]; const uint32_t used = off[w + 1] - off[w];
+    int32_t idx = 0;
+    for (uint32_t at = 0; at + HP_HDR <= used;) {
+      const uint32_t *e = p + at; const uint32_t nw = (e[HP_W_LEN] + 15u) / 16u;
+      if (nw > used - at - HP_HDR) break;                     // (never: hap_close counts whole entries)
+      lancet_haplotype x; memset(&x, 0, sizeof(x));
+      x.window = w; x.index_in_window = idx++; x.kmer = (uint16_t)(e[HP_W_KC] & 0xFFFFu); x.component = (uint16_t)(e[HP_W_KC] >> 16);
+      x.ref_off = e[HP_W_REFOFF]; x.ref_len = e[HP_W_REFLEN]; x.len = e[HP_W_LEN]; x.word_off = (uint32_t)r->words.size();
+      x.first_variant = (int32_t)e[HP_W_FIRST]; x.n_variants = (int32_t)e[HP_W_NVAR]; x.flags = e[HP_W_FLAGS];
+      r->words.insert(r->words.end(), e + HP_HDR, e + HP_HDR + nw);
+      r->h.push_back(x);
+      at += HP_HDR + nw;
+    }
+  }
 }
 static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const lancet_params *p, uint32_t evt_cap,
                                            uint32_t max_nodes_limit, int tier = 2) {

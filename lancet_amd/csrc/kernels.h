@@ -5372,10 +5372,53 @@ DEVNI bool repeats_in_graph_paths(Ctx &c) {
   return wg_bcast(&S.tmp0) == 2;
 }
 
+// Haplotype capture (lancet_engine_set_haplotypes; layout.h HP_*): the path string in W.pseq, m bases, becomes the next entry of the window's
+// buffer -- all lanes pack it 16 bases to a word, lane 0 writes the header.  The entry lies BEHIND the words the window's length word counts
+// and is counted by hap_close when the path's walk is through (the header's record count is known then); the length word lives in HBM, so
+// a window that is suspended between two k attempts carries nothing for it (the hand-over to the build service releases, the resume acquires:
+// try_suspend, window_kernel_body).  An entry that does not fit marks the window HP_TRUNC and
+// closes its buffer: nothing else about the window depends on it.  hd: the Hamming distance to the reference stretch, -1 for another length.
+DEVNI void hap_open(Ctx &c, int m, int hd, bool need_align) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const uint32_t cap = LC_CTX(c).C->hap_cap;
+  const int w = wg_uniform(S.w);
+  LC_GLOBAL uint32_t *lenp = LC_HAP_LEN(c) + w;
+  const uint32_t cur = (uint32_t)wg_uniform((int)ld2(lenp));
+  if (cur & HP_TRUNC) return;
+  const uint32_t nw = ((uint32_t)m + 15u) / 16u;
+  if (cur > cap || HP_HDR + nw > cap - cur) { WG_LANE0 { st2(lenp, cur | HP_TRUNC); } return; }
+  LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)w * cap + cur;
+  WG_FOR(i, nw) {
+    const int b0 = 16 * i, nb = m - b0 < 16 ? m - b0 : 16;
+    uint32_t v = 0;
+    for (int j = 0; j < nb; ++j) v |= (uint32_t)(W.pseq[b0 + j] & 3) << (2 * j);
+    p[HP_HDR + (uint32_t)i] = v;
+  }
+  WG_LANE0 {
+    p[HP_W_KC] = (uint32_t)S.K | ((uint32_t)W.gr[S.source].comp << 16);
+    p[HP_W_REFOFF] = (uint32_t)S.seq_t5; p[HP_W_REFLEN] = (uint32_t)S.seq_len; p[HP_W_LEN] = (uint32_t)m;
+    p[HP_W_FIRST] = (uint32_t)S.emit_seq; p[HP_W_NVAR] = 0;
+    p[HP_W_FLAGS] = (need_align ? 0u : LANCET_HAP_UNALIGNED) | (hd == 0 ? LANCET_HAP_IS_REF : 0u);
+    p[7] = 0;
+  }
+}
+// lane 0, after the path's walk: the records it emitted, and the entry counts
+DEV void hap_close(Ctx &c) {
+  LC_WS &S = LC_SREF(c);
+  const uint32_t cap = LC_CTX(c).C->hap_cap;
+  LC_GLOBAL uint32_t *lenp = LC_HAP_LEN(c) + S.w;
+  const uint32_t cur = ld2(lenp);
+  if (cur & HP_TRUNC) return;
+  LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)S.w * cap + cur;
+  p[HP_W_NVAR] = (uint32_t)S.emit_seq - p[HP_W_FIRST];
+  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u);
+}
+
 // eka (reference src/Graph.cc:1430-1501) via countRefPath (:2420-2445)
 DEVNI void count_ref_path(Ctx &c) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
   if (wg_bcastu(&S.source) == LC_NIL) return;
+  const bool hap_on = wg_uniform((int)LC_CTX(c).C->hap_cap) != 0;      // (haplotype capture: the one test of a run without it)
   if (wg_bcastu(&S.sink) != LC_NIL) {
     WG_LANE0 { evt(c, EV_SEARCH, (uint32_t)W.gr[S.source].comp); S.tmp0 = S.tmp1 = S.tmp2 = 0; S.part[0] = 0; S.part[1] = 0; S.part[2] = 0; S.part[3] = 0; S.pc_i = 0; S.pc_rd = 0; }
     const bool replay = wg_bcast(&S.pc_ok) != 0;             // the paths are the ones findRepeatsInGraphPaths found (pcache_store)
@@ -5441,6 +5484,8 @@ DEVNI void count_ref_path(Ctx &c) {
           if (n > (int)LC_CTX(c).C->max_w || n < 1 || m < 1) OVF(c);
           if (S.overflow) S.part[3] = 1;
         }
+        // the haplotype, where EV_ALN is written: once per path, whatever walks it
+        if (hap_on && wg_bcastu(&S.part[3]) == 0) hap_open(c, m, hd, need_align);
       }
       if (wg_bcastu(&S.part[3]) != 0) break;
       if (wg_bcastu(&S.part[6])) {
@@ -5470,6 +5515,7 @@ DEVNI void count_ref_path(Ctx &c) {
       }
       WG_LANE0 {
         if (!S.overflow) path_flag_edges(c, (int)S.part[4], 1u);
+        if (hap_on && !S.overflow) hap_close(c);
         if (S.overflow) S.part[3] = 1;
       }
       PHASE(c, 11);
@@ -5882,6 +5928,7 @@ DEV void process_window(Ctx &c, int w, int rq = -1) {
     if (LC_WIDE_IDS && !LC_CTX(c).C->wide_ids) S.overflow = 1;                                  // (a work space laid out for the 32-bit words)
     S.hasN = 0;
     S.nosusp_k = -1;
+    if (rq < 0 && LC_CTX(c).C->hap_cap) st2(LC_HAP_LEN(c) + w, 0u);      // haplotype capture: the window starts (the re-run tier: starts over)
     if (rq >= 0) {                                  // what the window carried when it was suspended
       LC_GLOBAL const SvcCont &ct = LC_CTX(c).OUT->svc->cont[rq];
       S.seq_t5 = ct.seq_t5; S.seq_len = ct.seq_len; S.trim5 = ct.trim5; S.trim3 = ct.trim3; S.emit_seq = ct.emit_seq;

@@ -23,6 +23,11 @@
 // -V / --more-verbose: -v plus the reference's -V lines (lancet_engine_set_trace_level, level 2): a diagnostics mode, every graph through the
 // general build.  The trace buffer is sized per batch (trace_words_for); windows whose trace did not fit say so in the text and are counted
 // on stderr.  The VCF is the one without the flag.
+// --haplotypes FILE: every assembled path of every window (lancet_engine_set_haplotypes) as FASTA, one record per haplotype in window processing
+// order: >chr:start-end|k=..|comp=..|path=..|ref=off+len|variants=first+n and the sequence on one line (ref: the stretch of the window reference
+// the path was compared with; variants: the window's records, in emission order, that this path emitted).  The buffer is sized per batch
+// (hap_words_for); windows whose haplotypes did not all fit are counted on stderr.  Not with --ranks above 1 (the gather carries records only);
+// the option is left out of ##cmdline: the VCF is byte for byte the one without it.
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
 
@@ -53,7 +58,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -62,6 +67,10 @@ const uint32_t MV_PATHS = 32;
 uint32_t trace_words_for(uint32_t longest, int max_indel_len) {
   const uint32_t w = 512u + MV_PATHS * ((longest + (uint32_t)max_indel_len + 256u + 3u) / 4u + 16u) + 16u * longest;
   return (w + 7u) / 8u * 8u;
+}
+// --haplotypes: words per window of such a batch: MV_PATHS haplotypes of up to longest + --max-indel-len + 256 bases, 16 bases to a word behind a header
+uint32_t hap_words_for(uint32_t longest, int max_indel_len) {
+  return MV_PATHS * ((uint32_t)LANCET_HAP_HEADER_WORDS + (longest + (uint32_t)max_indel_len + 256u + 15u) / 16u);
 }
 int die(const std::string &m) { fprintf(stderr, "lancet_gpu: %s\n", m.c_str()); return 1; }
 void usage() {
@@ -86,6 +95,8 @@ void usage() {
         "   --device-select                   : the alignments go to the GPU once and every batch's reads are picked there (LANCET_DEVICE_SELECT=1 does\n"
         "                                       the same); batches the device route does not take -- --linked-reads, --rg-file, reads left in the\n"
         "                                       graph by a window without mapped reads, oversize windows -- go the usual way; same VCF either way\n"
+        "   --haplotypes <file>               : every assembled path of every window as FASTA (>chr:start-end|k=|comp=|path=|ref=off+len|variants=first+n),\n"
+        "                                       at full throughput; same VCF, the option is left out of ##cmdline; not with --ranks above 1\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -100,7 +111,7 @@ int main(int argc, char **argv) {
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
-  std::string rendezvous;
+  std::string rendezvous, hap_file;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -130,13 +141,14 @@ int main(int argc, char **argv) {
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
-    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1;
+    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
   if (tumor.empty() || normal.empty() || ref.empty() || (reg.empty() && bed.empty())) { usage(); return die("--tumor, --normal, --ref and a region (--reg) or BED file (--bed) are required"); }
   if (kmer_recovery && ho.linked) return die("--kmer-recovery (-R) is not supported together with --linked-reads: the linked-read coverages come out of the barcode replay, where recovery is not built");
   if (ranks < 0 || (ranks == 0 && rank >= 0) || (ranks > 0 && rank >= ranks)) return die("--ranks must be >= 1 and --rank one of 0 .. ranks-1");
+  if (!hap_file.empty() && ranks > 1) return die("--haplotypes is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -240,7 +252,11 @@ int main(int argc, char **argv) {
     lancet_engine *e2 = nullptr;
     if (lancet_engine_create(&P, devs[0], &e2) == LANCET_OK) { if (verbose && !more_verbose) lancet_engine_set_trace(e2, 1u << 17); engs.push_back(e2); }
   }
-  struct Job { bool have = false; std::string trace; std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  FILE *hap_out = nullptr;
+  if (!hap_file.empty() && !(hap_out = fopen(hap_file.c_str(), "w"))) return die("cannot write " + hap_file);
+  const bool hap_on = hap_out != nullptr;
+  long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
@@ -290,6 +306,24 @@ int main(int argc, char **argv) {
         if (t) { j.trace += t; lancet_free(t); }
       }
     }
+    if (hap_on) {
+      const lancet_haplotype *hp; uint32_t nh = 0, nwords = 0; const uint32_t *words; const uint8_t *trunc;
+      if (lancet_engine_results_haplotypes(sl.e, &hp, &nh, &words, &nwords, &trunc) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+      for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
+      for (uint32_t i = 0; i < nh; ++i) {
+        const lancet_haplotype &x = hp[i];
+        if (x.window < 0 || x.window >= sl.nk || (uint64_t)x.word_off + (x.len + 15u) / 16u > nwords) continue;
+        char head[256];
+        snprintf(head, sizeof head, ">%s|k=%u|comp=%u|path=%d|ref=%u+%u|variants=%d+%d\n", lancet_host_window_hdr(H, sl.kept[(size_t)x.window]), (unsigned)x.kmer, (unsigned)x.component,
+                 x.index_in_window, x.ref_off, x.ref_len, x.first_variant, x.n_variants);
+        j.hapfa += head;
+        const size_t at = j.hapfa.size();
+        j.hapfa.resize(at + x.len + 1);
+        for (uint32_t b = 0; b < x.len; ++b) j.hapfa[at + b] = "ACGT"[(words[x.word_off + b / 16u] >> (2u * (b % 16u))) & 3u];
+        j.hapfa[at + x.len] = '\n';
+        ++n_hap;
+      }
+    }
     j.have = true; sl.chunk = -1;
     return true;
   };
@@ -298,6 +332,7 @@ int main(int argc, char **argv) {
     while (next_add < nchunks && jobs[(size_t)next_add].have) {
       Job &j = jobs[(size_t)next_add];
       if (!j.trace.empty()) fputs(j.trace.c_str(), stderr);
+      if (!j.hapfa.empty() && fwrite(j.hapfa.data(), 1, j.hapfa.size(), hap_out) != j.hapfa.size()) { fail = "cannot write " + hap_file; return false; }
       int arc = LANCET_OK;
       if (ranked) {                                  // the records travel: keyed, reduced, window numbers of the whole tiling
         if (!j.v.empty()) {
@@ -365,10 +400,11 @@ int main(int argc, char **argv) {
         lancet_window_slice SL;
         if (lancet_host_windows(H, lo, hi, &ho, &SL) != LANCET_OK) return die(lancet_host_last_error(H));
         t_batch += now() - t0; t0 = now();
-        if (more_verbose) {      // (the slice's windows: the batch's are among them)
+        if (more_verbose || hap_on) {      // (the slice's windows: the batch's are among them)
           uint32_t longest = 0;
           for (int32_t i = 0; i < SL.n_windows; ++i) longest = std::max(longest, SL.ref_off[i + 1] - SL.ref_off[i]);
-          if (lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+          if (more_verbose && lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+          if (hap_on && lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
         }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
         t_engine += now() - t0; t0 = now();
@@ -395,6 +431,11 @@ int main(int argc, char **argv) {
       sl.raw.assign((size_t)nk, std::string());
       for (int32_t w = 0; w < nk; ++w) { longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]); sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
       if (lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+    }
+    if (!taken && hap_on) {
+      uint32_t longest = 0;
+      for (int32_t w = 0; w < nk; ++w) longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]);
+      if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     t_engine += now() - t0;
@@ -424,6 +465,12 @@ int main(int argc, char **argv) {
   }
   if (more_verbose && n_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose -V trace did not fit its buffer (%u paths of the longest window reference + --max-indel-len bases): their text ends with a [trace truncated] line%s\n",
                                            n_truncated, MV_PATHS, ranked ? (" [rank " + std::to_string(rank) + "]").c_str() : "");
+  if (hap_on) {
+    if (fclose(hap_out) != 0) return die("cannot write " + hap_file);
+    fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, hap_file.c_str());
+    if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
+                                 n_hap_truncated, MV_PATHS, hap_file.c_str());
+  }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
   if (ranked) {
@@ -469,6 +516,7 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
+    if (strcmp(argv[i], "--haplotypes") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

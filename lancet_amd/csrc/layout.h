@@ -130,8 +130,21 @@ struct EngineCaps {
   uint32_t evt_level;    /* 1 = the reference's -v lines, 2 = its -V (--more-verbose) lines as well (kernels.h EV_REFID ...); 0 with tracing off */
   uint32_t todo_cap;     /* occurrences the mate-overlap prefilter may flag: table_cap in tier 1 (todo[] doubles as the slot -> node table), in the
                             re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
+  uint32_t hap_cap;      /* haplotype capture: words of the window's buffer (DevOut::hap_out), 0 = off (lancet_engine_set_haplotypes) */
   struct PreLayout pl;   /* hand-off areas of the LDS build kernel (below)                           */
 };
+
+/* ---- haplotype capture: one buffer of EngineCaps::hap_cap words per window, entries one behind the other in processPath order ----
+ * An entry is HP_HDR header words and the path string behind them, 16 bases to a word (2 bits per base, first base in the low bits).
+ * DevOut::hap_len[w] holds the words of the window's CLOSED entries: the entry of the path being walked lies behind them and counts
+ * once its walk is through (kernels.h hap_open / hap_close).  HP_TRUNC in that word: an entry did not fit, nothing is written after it. */
+#define HP_HDR 8u
+#define HP_TRUNC 0x80000000u
+enum { HP_W_KC = 0,        /* k | component << 16                                                      */
+       HP_W_REFOFF, HP_W_REFLEN,   /* Ref_t::seq as (offset into the window reference, length)         */
+       HP_W_LEN,           /* bases of the path string                                                 */
+       HP_W_FIRST, HP_W_NVAR,      /* seq_in_window of the path's first record, number of its records  */
+       HP_W_FLAGS };       /* LANCET_HAP_* ; word 7 is 0                                               */
 
 /* device-resident batch (after upload + prep) */
 struct DevBatch {
@@ -385,4 +398,18 @@ struct DevOut {
   LC_GLOBAL uint32_t *n_ahead_used;    /* atomic: window builds that took a graph built ahead                           */
   LC_GLOBAL const uint8_t *skip;       /* [n_windows] or null; non-zero: not this launch's window (a concurrent launch of the re-run tier has it) */
   LC_GLOBAL SvcCtl *svc;               /* build service of this launch, or null                                          */
+  LC_GLOBAL uint32_t *hap_len;         /* [n_windows] haplotype capture: words of the window's closed entries | HP_TRUNC (hap_cap != 0) */
+  LC_GLOBAL uint32_t *hap_out;         /* [n_windows * hap_cap]                                                          */
 };
+#ifdef LANCET_WAVE_EMU
+/* Host emulation of the kernels only: where the haplotype capture writes and how large a window's buffer is.  The emulator's driver
+ * fills a DevOut of its own; a test build that wants the capture sets this before the run (tests/hap_emu), lc_caps_for_sizes and the
+ * kernels read it in place of DevOut::hap_len / hap_out. */
+struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; };
+inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr};
+#define LC_HAP_LEN(c) (lc_emu_hap_sink.len)
+#define LC_HAP_OUT(c) (lc_emu_hap_sink.out)
+#else
+#define LC_HAP_LEN(c) (LC_CTX(c).OUT->hap_len)
+#define LC_HAP_OUT(c) (LC_CTX(c).OUT->hap_out)
+#endif

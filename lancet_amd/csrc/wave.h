@@ -79,6 +79,9 @@ template <class P> DEV uint32_t dev_atomic_cas32(P p, uint32_t cmp, uint32_t v) 
 }
 // load that bypasses the CU's vector L1 (performed at L2): for words that other lanes updated with atomics
 template <class P> DEV auto ld2(P p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ... and the store that goes with it: a word its own workgroup reads back with ld2.  No ordering and no fence -- a release at agent scope
+// writes the L2's dirty lines back, far too much for a word written once per path (st_rel below is for hand-overs between workgroups)
+template <class P> DEV void st2(P p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // acquire load / release store at agent scope: hand-over of plain data between workgroups of different kernels (build service)
 template <class P> DEV uint32_t ld_acq(P p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT); }
 template <class P> DEV void st_rel(P p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
@@ -136,6 +139,7 @@ DEV unsigned long long dev_atomic_cas64(unsigned long long *p, unsigned long lon
 DEV uint32_t dev_atomic_cas32(uint32_t *p, uint32_t cmp, uint32_t v) { uint32_t o = *p; if (o == cmp) *p = v; return o; }
 DEV uint32_t ld2(const uint32_t *p) { return *p; }
 DEV unsigned long long ld2(const unsigned long long *p) { return *p; }
+DEV void st2(uint32_t *p, uint32_t v) { *p = v; }
 DEV uint32_t ld_acq(const uint32_t *p) { return *p; }
 DEV void st_rel(uint32_t *p, uint32_t v) { *p = v; }
 DEV uint32_t add_rel(uint32_t *p, uint32_t v) { uint32_t o = *p; *p = o + v; return o; }

@@ -73,6 +73,11 @@ def lib():
         L.lancet_engine_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float * 2)]
         L.lancet_engine_results_lr.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetVariantLR)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lancet_engine_set_trace.argtypes = [C.c_void_p, C.c_uint32]
+        L.lancet_engine_set_haplotypes.argtypes = [C.c_void_p, C.c_uint32]
+        L.lancet_engine_results_haplotypes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetHaplotype)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
+                                                       C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint8))]
+        L.lancet_engine_haplotype_readback_ms.restype = C.c_float
+        L.lancet_engine_haplotype_readback_ms.argtypes = [C.c_void_p]
         L.lancet_engine_set_trace_level.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
         L.lancet_engine_trace_level.argtypes = [C.c_void_p]
         L.lancet_engine_trace.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
@@ -147,9 +152,10 @@ class DeviceReads:
 
 
 class Engine:
-    def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1):
+    def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1, haplotype_words: int = 0):
         """trace_words: 32-bit words of trace events kept per window (0: no trace).  trace_level 1: the reference's -v lines; 2: its -V
-        (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level)."""
+        (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level).
+        haplotype_words: 32-bit words kept per window for its assembled haplotypes (0: none; lancet_engine_set_haplotypes, haplotypes())."""
         self.L = lib()
         self.params = params or abi.default_params()
         h = C.c_void_p()
@@ -164,6 +170,24 @@ class Engine:
             self._chk(self.L.lancet_engine_set_trace_level(self.h, trace_words, 2))
         elif trace_words:
             self.L.lancet_engine_set_trace(self.h, trace_words)
+        if haplotype_words:
+            self.set_haplotypes(haplotype_words)
+
+    def set_haplotypes(self, words_per_window: int) -> None:
+        """lancet_engine_set_haplotypes: for the uploads that follow (0: off).  EngineError between an upload and its run."""
+        self._chk(self.L.lancet_engine_set_haplotypes(self.h, words_per_window))
+
+    def haplotypes(self):
+        """(haplotypes, truncated) of the last run: abi.haplotypes_to_py's dicts ordered by (window, index), and per window 1 where some of its
+        haplotypes did not fit.  Both empty / all zero with the capture off."""
+        hp, n, wp, nwd, tp = C.POINTER(abi.LancetHaplotype)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint8)()
+        self._chk(self.L.lancet_engine_results_haplotypes(self.h, C.byref(hp), C.byref(n), C.byref(wp), C.byref(nwd), C.byref(tp)))
+        words = np.ctypeslib.as_array(wp, shape=(nwd.value,)).copy() if nwd.value else np.zeros(0, np.uint32)
+        nw = self._batch.n_windows if self._batch is not None else 0
+        return abi.haplotypes_to_py(hp, n.value, words), [int(tp[w]) for w in range(nw)]
+
+    def haplotype_readback_ms(self) -> float:
+        return float(self.L.lancet_engine_haplotype_readback_ms(self.h))
 
     def _chk(self, rc):
         if rc != 0:
