@@ -891,7 +891,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   const int reflen = (int)(B.ref_off[w + 1] - B.ref_off[w]);
   LC_GLOBAL const uint8_t *refc = B.ref_codes + B.ref_off[w];
   WG_LANE0 { S.hint = 0; S.ndup = 0; S.w = w; S.why = BLW_NONE; S.R = nr + 1; S.reflen = reflen; S.hasN = 0; S.mapped = 0; S.flagged = 0; S.npairs = 0; S.edges_total = 0; S.refn = 0;
-             H->status = PB_NOT_BUILT; H->why = 0; H->have_rep = 0; H->heavy = 0; H->next = 0; H->lr = 0; H->lr_total = 0;
+             H->status = PB_NOT_BUILT; H->why = 0; H->have_rep = 0; H->heavy = 0; H->next = 0; H->lr = 0; H->lr_total = 0; H->settled = 0;
              ((LC_GLOBAL PreCmp *)(area + PRE_OFF_CHDR))->done = 0;
              if (nr > BL_RMAX || reflen > (int)PL.maxw || reflen < 1) S.why = BLW_SIZE; }
   if (bl_bcast(&S.why)) { WG_LANE0 { H->why = (uint32_t)S.why; } return; }
@@ -2022,15 +2022,59 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
       WG_SYNC();
     }
   }
+  // ---- settled windows ("Settled windows"; layout.h PreHdr::settled): the survivors are the nodes of one run [a, b] of
+  //      reference offsets, each at one offset only, and every one's filtered edge list is exactly the two links (one at the ends of the run)
+  //      that the reference pseudo-read's own steps made.  Such a graph is one component without a cycle whose source -> sink paths all spell
+  //      the window reference: the window ends at this k with no record, whatever the coverages are, and nothing below is needed for it.
+  //      Two passes over the reference offsets; the words are the edge slots' area above, free again.
+  bool settled = false;
+  if (C->settle && !rep && K <= 31 && !(BL_WIDE != 0 && N > 4096u) && nsurv > 0 && !hasN && !P->lr_mode && C->debug_stop == 0u && !C->evt_cap && !C->hap_cap &&
+      reflen - K + 1 > 0 && reflen - K + 1 <= (int)LC_MAXW && nsurv <= (uint32_t)(reflen - K + 1)) {
+    static_assert(BL_BIG / 4u >= BL_NCAP / 32u + BL_NCAP / 4u + 4u + (uint32_t)LC_MAXW, "words of the settled test");
+    LC_LDS uint32_t *T = S.big + BL_NCAP / 32 + BL_NCAP / 4;       // [0] a, [1] b, [2] a rule is broken
+    LC_LDS uint32_t *own = T + 4;                                  // [nsurv] first reference offset of survivor si
+    LC_GLOBAL const NodeGr *pgr = (LC_GLOBAL const NodeGr *)(area + PRE_OFF_PGR);
+    const int nrefk = reflen - K + 1;
+    const uint32_t rb = 16u * S.rdo[nr];
+    WG_SYNC();
+    WG_LANE0 { T[0] = LC_NIL; T[1] = 0; T[2] = 0; }
+    WG_FOR(si, nsurv) { own[si] = LC_NIL; }
+    WG_SYNC();
+    WG_FOR(i, nrefk) {
+      const uint32_t si = S.cidx[X.occn[rb + (uint32_t)i] & ON_ID];
+      if (si != 0xFFFFu) { dev_atomic_min(&own[si], (uint32_t)i); dev_atomic_min(&T[0], (uint32_t)i); dev_atomic_max(&T[1], (uint32_t)i); }
+    }
+    WG_SYNC();
+    const uint32_t a = bl_bcast(&T[0]), b = bl_bcast(&T[1]);
+    if (a != LC_NIL && b - a + 1u == nsurv) {                      // (with every offset of [a, b] a survivor's first: the run's nodes are all the survivors)
+      WG_FOR(i, nrefk) {
+        if ((uint32_t)i < a || (uint32_t)i > b) continue;
+        const uint32_t e = X.occn[rb + (uint32_t)i], si = S.cidx[e & ON_ID], o = (e >> ON_ORISH) & 1u;
+        bool ok = si != 0xFFFFu && own[si] == (uint32_t)i;
+        if (ok) {
+          uint32_t want[2] = {0u, 0u}; uint32_t nw = 0;              // the links of the steps i -> i + 1 (this node is u) and i - 1 -> i (it is v), as the edge pass resolves them
+          if ((uint32_t)i < b) { const uint32_t e2 = X.occn[rb + (uint32_t)i + 1u], o2 = (e2 >> ON_ORISH) & 1u; want[nw++] = ED_MAKE(e2 & ON_ID, o == 0 ? (o2 == 0 ? 0u : 1u) : (o2 == 0 ? 2u : 3u)); }
+          if ((uint32_t)i > a) { const uint32_t e0 = X.occn[rb + (uint32_t)i - 1u], o0 = (e0 >> ON_ORISH) & 1u; want[nw++] = ED_MAKE(e0 & ON_ID, o0 == 0 ? (o == 0 ? 3u : 1u) : (o == 0 ? 2u : 0u)); }
+          LC_GLOBAL const NodeGr &G = pgr[si];
+          if (G.necnt != nw) ok = false;
+          else if (nw == 1u) ok = G.edges[0] == want[0];
+          else if (nw == 2u) ok = (G.edges[0] == want[0] && G.edges[1] == want[1]) || (G.edges[0] == want[1] && G.edges[1] == want[0]);
+        }
+        if (!ok) T[2] = 1u;
+      }
+      WG_SYNC();
+      settled = bl_bcast(&T[2]) == 0u;
+    }
+  }
   BLP(S, 15);
   BL_TAIL_PRIO_SET(BL_TAIL_PRIO);
   // ---- libstdc++ iteration order of the node table after the N inserts (kernels.h first_lowcov / order_stage),
   //      reduced to the survivors (cleanDead), and markConnectedComponents over them -- all in LDS: the reads are done with, the
   //      whole arena from S.bases to the end of S.big is laid out anew.  Tables of more than 4096 nodes: the 1024-lane configuration, whose
   //      arena holds the arrays for its BL_NCAP nodes once the bucket minima and the run counters are 16-bit halves (below); else the window kernel.
-  WG_LANE0 { H->have_order = 0; }
+  WG_LANE0 { H->have_order = 0; H->settled = settled ? 1u : 0u; }
   const bool wide_tab = BL_WIDE != 0 && N > 4096u;
-  if ((N <= 4096u || (wide_tab && N <= BL_NCAP)) && nsurv > 0) {
+  if (!settled && (N <= 4096u || (wide_tab && N <= BL_NCAP)) && nsurv > 0) {
     LC_LDS uint8_t *arena = (LC_LDS uint8_t *)&S.bases[0];
     LC_LDS uint32_t *first = (LC_LDS uint32_t *)arena;                       // [5120] smallest position of a bucket's elements
     LC_LDS uint32_t *tmp = first + 5120;                                     // [4104] run sizes -> run starts -> fill cursors
@@ -2287,7 +2331,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   BL_TAIL_PRIO_SET(0);
   WG_LANE0 {
     H->K = K; H->refE = S.repE; H->refM = S.repM; H->N = S.N; H->O = S.O; H->totalreadbp = S.totalreadbp; H->n_kmers = S.n_kmers;
-    H->ncand = S.ncand; H->nsurv = S.nsurv; H->edges_total = S.edges_total; H->refn = S.refn; H->why = 0; H->heavy = S.hint;
+    H->ncand = S.ncand; H->nsurv = S.nsurv; H->edges_total = S.edges_total; H->refn = S.refn; H->why = 0; H->heavy = settled ? 0u : S.hint;      // (a settled window: a chain has no cycle, nothing is built ahead)
     H->big = BL_WG > 512 ? 1u : 0u;
     H->status = PB_BUILT;
   }
@@ -2302,7 +2346,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
 // ahead), into an area of `pool` (pool_cap areas, handed out by queue[2]); PreHdr::next links them.  A graph built ahead that
 // the window kernel does not ask for is wasted work, nothing else: results never depend on what was built ahead.
 // (queue[0] = next window, queue[1] = windows built, queue[2] = pool areas handed out, queue[3] = graphs built ahead,
-//  queue[4] = windows on `biglist`, queue[5] = next entry of it, queue[7] = windows finished -- built, listed or turned away)
+//  queue[4] = windows on `biglist`, queue[5] = next entry of it, queue[6] = windows settled here (PreHdr::settled), queue[7] = windows finished -- built, listed or turned away)
 // The workgroups of the build service (svc_kernel_body) work the same queue off until it is empty, before they serve their first
 // request; the kernel that the window kernel is ordered behind is this one, so its workgroups leave only when every window handed
 // out -- to either kernel -- is finished (`helpers`: queue[7], released by whoever finished the window).
@@ -2361,7 +2405,7 @@ DEV void build_kernel_body(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
 #endif
     WG_LANE0 {
       LC_GLOBAL const PreHdr *Hw = (LC_GLOBAL const PreHdr *)(pre + (size_t)w * PRE_STRIDE);
-      if (Hw->status == PB_BUILT) dev_atomic_add(queue + 1, 1u);
+      if (Hw->status == PB_BUILT) { dev_atomic_add(queue + 1, 1u); if (Hw->settled) dev_atomic_add(queue + 6, 1u); }
       else if (!from_list && biglist && (Hw->why == (uint32_t)BLW_SIZE || Hw->why == (uint32_t)BLW_KBIG)) biglist[dev_atomic_add(queue + 4, 1u)] = (uint32_t)w;
     }
     WG_SYNC();                                                     // (every lane's stores to the hand-off area are issued ...)

@@ -121,13 +121,14 @@ __global__ void svc_done_kernel(SvcCtl *sv) { __hip_atomic_store(&sv->done, 1u, 
 //   a read repeats a k-mer (`heavy`: k will climb, 2+ builds)   2.1 ms, up to 6
 //   first compress not done here (several components)           1.3 ms .. 2.9 ms by the number of survivors
 //   first compress done: nodes left in the table                3 .. 5: 0.35 ms (no bubble: nothing to align), 8: 1.1 ms, 11: 1.7 ms, 16: 2.6 ms
-//   no reads / no k                                             0.1 ms                 last
+//   no reads / no k, settled by the build kernel (PreHdr::settled)   0.1 ms and less     last
 // Only the order changes; results are sorted by (window, emission) afterwards.
 #define ORD_CLASSES 32
-#define LC_COUNTER_BYTES 512            /* u32: 0..3 results, 2 the window kernel's queue head, 8..15 the build kernels', 32..63 windows per class, 64..95 places given out per class */
+#define LC_COUNTER_BYTES 512            /* u32: 0..3 results, 2 the window kernel's queue head, 8..15 the build kernels' (14: windows settled there), 16 graphs built ahead that were taken, 32..63 windows per class, 64..95 places given out per class */
 __device__ uint32_t order_class(const uint8_t *area, uint32_t chdr) {
   const PreHdr *H = (const PreHdr *)(area + PRE_OFF_HDR);
   if (H->status != PB_BUILT) return (H->why == BLW_NOREADS || H->why == BLW_K) ? 0u : 31u;
+  if (H->settled) return 0u;                       // (settled by the build kernel: the window kernel reads its header and is through)
   if (H->heavy) return 26u;
   const PreCmp *Cm = (const PreCmp *)(area + chdr);
   if (Cm->done) {
@@ -292,6 +293,8 @@ struct lancet_engine {
   int n_bslots_large = 0, n_biglist = -1;          // n_biglist: windows the last batch handed to the 1024-lane configuration (-1: no batch yet)
   uint32_t pool_cap = 0; int ahead_depth = 6;      // graphs built ahead for windows whose k will climb (build_lds.h, build_kernel_body)
   int n_ahead_built = 0, n_ahead_used = 0;
+  int n_settled = 0;          // windows of the last run that the build kernel settled (PreHdr::settled)
+  bool no_settle = false;     // LANCET_NO_SETTLE=1: EngineCaps::settle stays 0
   bool heavy_first = true;    // LANCET_NO_HEAVY_FIRST=1: windows in batch order
   int order_mode = 0;         // LANCET_ORDER=two: two classes only (see order_class)
   unsigned long long blphase[16] = {0};
@@ -452,6 +455,7 @@ int lancet_engine_create(const lancet_params *p, int device, lancet_engine **out
   e->up_timing = getenv("LANCET_UPLOAD_TIMING") != nullptr;
   e->phase_times = getenv("LANCET_PHASE_TIMES") != nullptr && atoi(getenv("LANCET_PHASE_TIMES")) != 0;      // per-phase tick accounting of both kernels (tools/quick_gpu.py ...): clock reads per phase and contended atomics per window otherwise
   e->dbg = getenv("LANCET_DEBUG") != nullptr; e->no_fat = getenv("LANCET_NO_FAT") != nullptr; e->no_early_rerun = getenv("LANCET_NO_EARLY_RERUN") != nullptr;
+  e->no_settle = getenv("LANCET_NO_SETTLE") != nullptr && atoi(getenv("LANCET_NO_SETTLE")) != 0;
   e->no_large_build = getenv("LANCET_NO_LARGE_BUILD") != nullptr; e->heavy_first = getenv("LANCET_NO_HEAVY_FIRST") == nullptr;
   if (const char *s = getenv("LANCET_ORDER")) e->order_mode = strcmp(s, "two") == 0 ? 1 : 0;
   if (const char *s = getenv("LANCET_BUILD_SLOTS")) e->build_slots_env = std::max(1, atoi(s));
@@ -609,6 +613,8 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   }
   e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
   e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
+  // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
+  e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? 1u : 0u;
 }
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk) {
   if (!e || !b || b->n_windows < 0) return LANCET_E_ARG;
@@ -928,7 +934,7 @@ static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatc
       e->svc_host.cont = (LC_GLOBAL SvcCont *)((char *)e->d_svc.p + off_cont);
       o.svc = (LC_GLOBAL SvcCtl *)e->d_svc.p;
     }
-    if (e->pool_cap) { ENS(e->d_prepool, (size_t)e->pool_cap * e->caps.pl.stride); tick("pool of hand-off areas", (size_t)e->pool_cap * e->caps.pl.stride); o.pre_pool = (LC_GLOBAL const uint8_t *)e->d_prepool.p; o.n_ahead_used = (LC_GLOBAL uint32_t *)e->d_counters.p + 14; }
+    if (e->pool_cap) { ENS(e->d_prepool, (size_t)e->pool_cap * e->caps.pl.stride); tick("pool of hand-off areas", (size_t)e->pool_cap * e->caps.pl.stride); o.pre_pool = (LC_GLOBAL const uint8_t *)e->d_prepool.p; o.n_ahead_used = (LC_GLOBAL uint32_t *)e->d_counters.p + 16; }
   }
   UP(e->d_out, &o, sizeof(o));
   DBG("sync");
@@ -1255,7 +1261,7 @@ int lancet_engine_submit(lancet_engine *e) {
   HIPCHK(e, hipMemsetAsync(e->d_counters.p, 0, LC_COUNTER_BYTES, e->stream));
   HIPCHK(e, hipMemsetAsync(e->d_stats.p, 0, sizeof(lancet_window_stats) * e->n_windows, e->stream));
   if (e->prebuild) HIPCHK(e, hipMemsetAsync(e->d_blphase.p, 0, 16 * sizeof(unsigned long long), e->stream));      // (before the service starts: its workgroups add to it too)
-  e->ms_build = 0; e->n_prebuilt = 0;
+  e->ms_build = 0; e->n_prebuilt = 0; e->n_settled = 0;
   e->fat_inflight = false; e->ms_fat = 0;
   e->svc_running = false;
   if (e->svc_cap) {                // the build service takes its place on the GPU before the batch's kernels
@@ -1340,9 +1346,9 @@ int lancet_engine_wait(lancet_engine *e) {
   }
   if (e->prebuild) {
     HIPCHK(e, hipEventElapsedTime(&e->ms_build, e->evb0, e->evb1));
-    uint32_t bq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t bq[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     HIPCHK(e, lc_copy(e, bq, (uint32_t *)e->d_counters.p + 8, sizeof(bq), hipMemcpyDeviceToHost));
-    e->n_prebuilt = (int)bq[1]; e->n_ahead_built = (int)bq[3]; e->n_ahead_used = (int)bq[6]; e->n_biglist = (int)bq[4];
+    e->n_prebuilt = (int)bq[1]; e->n_ahead_built = (int)bq[3]; e->n_ahead_used = (int)bq[8]; e->n_biglist = (int)bq[4]; e->n_settled = (int)bq[6];
     if (e->phase_times) HIPCHK(e, lc_copy(e, e->blphase, e->d_blphase.p, sizeof(e->blphase), hipMemcpyDeviceToHost)); else memset(e->blphase, 0, sizeof(e->blphase));
   }
   if (e->ms_fat > e->ms_window + e->ms_build) e->ms_window = e->ms_fat - e->ms_build;    // both started together: the window kernels' time is the longer of the two
@@ -1588,6 +1594,7 @@ int lancet_engine_build_phase_times(lancet_engine *e, const unsigned long long *
 }
 // windows of the last run whose first graph came from the LDS build kernel (windows with N in their reference among them)
 int lancet_engine_prebuilt_count(lancet_engine *e) { return e ? e->n_prebuilt : -1; }
+int lancet_engine_settled_count(lancet_engine *e) { return e ? e->n_settled : -1; }
 
 // test/tuning hook: the hand-off headers of the last run (status | why << 8 | table order and components came along << 16, K, heavy, N, nsurv, numcomp, ncand, next per window)
 int lancet_debug_pre_headers(lancet_engine *e, uint32_t *out) {

@@ -67,7 +67,7 @@ static inline PreLayout lc_pre_layout_for_batch(const lancet_window_batch *b, si
 
 // Test hook (engine.hip lancet_debug_pre_order and its twin in tests/emu/emu_engine.cc): what ONE hand-off area -- a host copy of it -- says
 // about the table order, appended to `out`:
-//   K, status, N, nsurv, have_order, ht_bc, ht_next_resize, numcomp, refcomp, big, PreCmp::done, m_live          (12 words)
+//   K, status, N, nsurv, have_order, ht_bc, ht_next_resize, numcomp, refcomp, big, PreCmp::done, m_live, settled (13 words)
 //   with have_order, per table position i < nsurv: nhash[order[i]] (low, high word), the comp of that survivor's record
 //   with done, per position i < m_live of CLIVE: the hash of the node there (low, high; a special node's is PreCmp::spec_hash)
 // Returns PreHdr::next (0: the last graph of the window's chain), -1 when an index in the area points outside its array.
@@ -75,9 +75,9 @@ static inline int lc_pre_order_words(const uint8_t *area, const PreLayout &pl, s
   const PreHdr *H = (const PreHdr *)(area + PRE_OFF_HDR);
   const PreCmp *CH = (const PreCmp *)(area + pl.chdr);
   const bool built = H->status == PB_BUILT, ord = built && H->have_order == 1u, done = ord && CH->done == 1u;
-  const uint32_t hdr[12] = {(uint32_t)H->K, H->status, built ? H->N : 0u, built ? H->nsurv : 0u, ord ? 1u : 0u, ord ? H->ht_bc : 0u, ord ? H->ht_next_resize : 0u,
-                            ord ? H->numcomp : 0u, ord ? H->refcomp : 0u, built ? H->big : 0u, done ? 1u : 0u, done ? CH->m_live : 0u};
-  out->insert(out->end(), hdr, hdr + 12);
+  const uint32_t hdr[13] = {(uint32_t)H->K, H->status, built ? H->N : 0u, built ? H->nsurv : 0u, ord ? 1u : 0u, ord ? H->ht_bc : 0u, ord ? H->ht_next_resize : 0u,
+                            ord ? H->numcomp : 0u, ord ? H->refcomp : 0u, built ? H->big : 0u, done ? 1u : 0u, done ? CH->m_live : 0u, (built && H->settled == 1u) ? 1u : 0u};
+  out->insert(out->end(), hdr, hdr + 13);
   if (!ord) return (int)H->next;
   const unsigned long long *nhash = (const unsigned long long *)(area + pl.nhash);
   const uint32_t *sid = (const uint32_t *)(area + pl.sid), *order = (const uint32_t *)(area + pl.order), *clive = (const uint32_t *)(area + pl.clive);
@@ -180,6 +180,8 @@ static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_
   c.pl = lc_pre_layout(PB_NCAP, PB_QVCAP, 1u, c.max_w);      // (the engine replaces it per upload: lc_pre_layout_for_batch)
 #ifdef LANCET_WAVE_EMU
   c.hap_cap = lc_emu_hap_sink.cap;                            // (the engine sets it from lancet_engine_set_haplotypes)
+  // settled windows: off unless the emulation is told otherwise, and then by the engine's rule (engine.hip lc_upload_caps: no trace, no capture, no linked reads)
+  { const char *sv = getenv("LANCET_EMU_SETTLE"); c.settle = (sv && atoi(sv) == 1 && !evt_cap && !c.hap_cap && !c.lr_mode) ? 1u : 0u; }
 #endif
   return c;
 }

@@ -19,20 +19,20 @@ _LIB = None
 ERRORS = {0: "OK", -1: "bad argument", -2: "no HIP device", -3: "HIP error", -4: "unsupported", -5: "out of memory", -6: "bad state"}
 
 
-PRE_ORDER_WORDS = 64 * (12 + 3 * 2048 + 2 * 834)      # room for Engine.pre_order: a chain of 64 graphs at the hand-off limits
+PRE_ORDER_WORDS = 64 * (13 + 3 * 2048 + 2 * 834)      # room for Engine.pre_order: a chain of 64 graphs at the hand-off limits
 
 
 def parse_pre_order(words):
     """The words of lancet_debug_pre_order (csrc/host_common.h lc_pre_order_words) as one dict per graph: K, built, N, nsurv, have_order,
-    ht_bc, ht_next_resize, numcomp, refcomp, big, done, m_live; with have_order `hashes` (uint64 per table position) and `comp`; with
+    ht_bc, ht_next_resize, numcomp, refcomp, big, done, m_live, settled; with have_order `hashes` (uint64 per table position) and `comp`; with
     done `live_hashes` (the table after markRefEnds(1) and compress(1), special nodes included)."""
     import numpy as np
     graphs, at = [], 0
-    names = ("K", "status", "N", "nsurv", "have_order", "ht_bc", "ht_next_resize", "numcomp", "refcomp", "big", "done", "m_live")
+    names = ("K", "status", "N", "nsurv", "have_order", "ht_bc", "ht_next_resize", "numcomp", "refcomp", "big", "done", "m_live", "settled")
     while at < len(words):
-        g = {k: int(v) for k, v in zip(names, words[at:at + 12])}
+        g = {k: int(v) for k, v in zip(names, words[at:at + 13])}
         g["built"] = g.pop("status") == 1
-        at += 12
+        at += 13
         if g["have_order"]:
             rows = np.asarray(words[at:at + 3 * g["nsurv"]], dtype=np.uint64).reshape(g["nsurv"], 3)
             g["hashes"] = rows[:, 0] | (rows[:, 1] << np.uint64(32))
@@ -83,6 +83,7 @@ def lib():
         L.lancet_engine_trace.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lancet_engine_rerun_count.argtypes = [C.c_void_p]
         L.lancet_engine_prebuilt_count.argtypes = [C.c_void_p]
+        L.lancet_engine_settled_count.argtypes = [C.c_void_p]
         L.lancet_engine_ahead_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.lancet_engine_svc_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32 * 4)]
         L.lancet_engine_build_phase_times.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]
@@ -350,6 +351,10 @@ class Engine:
 
     def prebuilt_count(self) -> int:
         return int(self.L.lancet_engine_prebuilt_count(self.h))
+
+    def settled_count(self) -> int:
+        """Windows of the last run that the build kernel settled (reference-only chains: no record, nothing loaded by the window kernel)."""
+        return int(self.L.lancet_engine_settled_count(self.h))
 
     def pre_headers(self):
         """test hook: per window of the last run (built in LDS, K, nodes, table order + components came along) from the hand-off headers"""
