@@ -353,8 +353,9 @@ int lancet_engine_kernel_times(lancet_engine *e, float *ms, int cap);
 /* Windows of the last run whose first graph was assembled by the LDS build kernel (the others took the general build phases). */
 int lancet_engine_prebuilt_count(lancet_engine *e);
 /* Windows of the last run that the build kernel SETTLED: the graph after the first removeLowCov was the window reference's own k-mers in
- * one chain and nothing else, so the window ended at that k with no record and the window kernel loaded nothing of it.  0 whenever the
- * trace, the haplotype capture or --linked-reads is on, or LANCET_NO_SETTLE=1 is in the environment.  Results never depend on it. */
+ * one chain, beside components without a node for markRefEnds to start from at most, so the window ended at that k with no record and the
+ * window kernel loaded nothing of it.  0 whenever the trace, the haplotype capture or --linked-reads is on, or LANCET_NO_SETTLE=1 is in the
+ * environment; with LANCET_SETTLE_CHAIN_ONLY=1 only windows whose chain is the whole graph.  Results never depend on it. */
 int lancet_engine_settled_count(lancet_engine *e);
 /* Graphs the build kernel built AHEAD in the last run -- the next k of a window whose graph at the current k holds a k-mer twice
  * in one read and will be rejected (reference src/Microassembler.cc:198-206: cycle -> next k) -- and how many of them the window

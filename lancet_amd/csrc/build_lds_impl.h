@@ -1842,6 +1842,19 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   }
   BLP(S, 12);
   if (C->debug_stop == 112u) { WG_LANE0 { H->why = 99; } return; }
+  // ---- settled windows (further down): may this graph be settled at all, and the words of the test -- between the mer-table bitmap and the edge
+  //      slots, the trace's edge masks otherwise (settling is off with the trace): they live from the pass over the reference offsets below, through
+  //      every group of the edge pass, to the verdict behind it.
+  LC_LDS uint32_t *ST = S.big + BL_NCAP / 32;                      // [0] a rule is broken
+  LC_LDS uint32_t *st_sb = ST + 4;                                 // [LC_MAXW / 32] bit i: the node of reference offset i survives
+  LC_LDS uint32_t *st_ok = st_sb + LC_MAXW / 32;                   // ... i is its node's first offset and the node's edges are exactly the links to the surviving offsets i - 1, i + 1
+  LC_LDS uint32_t *st_q = st_ok + LC_MAXW / 32;                    // ... its node has getTotCov() >= COV_THRESHOLD (a node at one offset only; at several: ST[0])
+  LC_LDS uint32_t *st_multi = st_q + LC_MAXW / 32;                 // [PB_SCAP / 32] bit si: survivor si is at more than one reference offset
+  LC_LDS uint32_t *st_own = st_multi + PB_SCAP / 32;               // [nsurv] first reference offset of survivor si
+  constexpr uint32_t ST_FIXED = 4u + 3u * ((uint32_t)LC_MAXW / 32u) + PB_SCAP / 32u;
+  static_assert(BL_NCAP / 4u > ST_FIXED + 512u, "words of the settled test");
+  const bool try_settle = C->settle && !rep && K <= 31 && !(BL_WIDE != 0 && N > 4096u) && nsurv > 0 && nsurv <= PB_SCAP && nsurv <= BL_NCAP / 4u - ST_FIXED && !hasN &&
+                          !P->lr_mode && C->debug_stop == 0u && !C->evt_cap && !C->hap_cap && reflen - K > 0 && reflen - K + 1 <= (int)LC_MAXW;      // (a reference of more than K bases: it has k-mers, nrefk of them)
   // ---- Ref_t::mertable membership, Ref_t::computeCoverage (src/Ref.cc:40-64, 173-250) from the counts of the tracked nodes, the
   //      reference pseudo-read's node per offset.  First build of the window: Ref_t::seq is still the whole rawseq.
   {
@@ -1875,6 +1888,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
     LC_LDS uint32_t *inm2 = S.big + BL_NCAP / 32;                  // INMER per survivor: keep a copy of the bitmap while cidx changes meaning
     (void)inm2;
     WG_FOR(n, N) { S.cidx[n] = 0xFFFFu; }
+    if (try_settle) { WG_FOR(i, ST_FIXED + nsurv) { ST[i] = (uint32_t)i < ST_FIXED ? 0u : LC_NIL; } }
     WG_SYNC();
     WG_FOR(si, nsurv) { S.cidx[X.c_id[X.s_ci[si]]] = (uint16_t)si; }
     WG_SYNC();
@@ -1887,7 +1901,12 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
     WG_FOR(i, nrefk) {
       const uint32_t e = X.occn[rb + (uint32_t)i];
       const uint32_t n = e & ON_ID;
-      occ_ref[i] = n | (S.cidx[n] != 0xFFFFu ? 0u : PB_GONE) | ((e & ON_ORI) ? 0x80000000u : 0u);
+      const uint32_t si = S.cidx[n];
+      occ_ref[i] = n | (si != 0xFFFFu ? 0u : PB_GONE) | ((e & ON_ORI) ? 0x80000000u : 0u);
+      if (try_settle && si != 0xFFFFu) {                             // the settled test's view of the offsets: who survives, each survivor's first, who is met again
+        dev_atomic_or(&st_sb[(uint32_t)i >> 5], 1u << ((uint32_t)i & 31u));
+        if (dev_atomic_min(&st_own[si], (uint32_t)i) != LC_NIL) dev_atomic_or(&st_multi[si >> 5], 1u << (si & 31u));
+      }
     }
   }
   BLP(S, 13);
@@ -1991,6 +2010,7 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
         for (int i = 1; i < ne; ++i) { const uint32_t s = stamp[i]; int j = i; while (j > 0 && stamp[j - 1] > s) { stamp[j] = stamp[j - 1]; --j; } stamp[j] = s; }
         LC_GLOBAL NodeGr &G = pgr[si];
         int m = 0;
+        uint32_t ed0 = 0, ed1 = 0;                                   // (the settled test: the first two links of the filtered list)
         for (int i = 0; i < ne; ++i) {
           const uint32_t s = stamp[i] >> 1;
           const uint32_t a = X.occn[s], b = X.occn[s + 1];           // u and v of that step
@@ -2000,7 +2020,9 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
           else { to = a & ON_ID; dir = ua == 0 ? (ub == 0 ? 3u : 1u) : (ub == 0 ? 2u : 0u); }                         // RR FR RF FF
           if (S.cidx[to] == 0xFFFFu) continue;                       // removeNode of a non-survivor took the edge with it
           X.s_edges[9 * (size_t)si + (uint32_t)m] = S.cidx[to];     // (neighbour by survivor index: the component search below)
-          G.edges[m++] = ED_MAKE(to, dir);
+          const uint32_t ed = ED_MAKE(to, dir);
+          if (m == 0) ed0 = ed; else if (m == 1) ed1 = ed;
+          G.edges[m++] = ed;
         }
         for (int i = m; i < 8; ++i) X.s_edges[9 * (size_t)si + (uint32_t)i] = 0xFFFFu;
         X.s_edges[9 * (size_t)si + 8] = ((inmer[n >> 5] >> (n & 31u)) & 1u);
@@ -2015,6 +2037,30 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
         G.cov[0] = (float)(c0 + (rv & 0xFFFFu)); G.cov[1] = (float)(c1 + (rv >> 16)); G.cov[2] = (float)c2; G.cov[3] = (float)c3;      // (kc: the cov_t counts, which -R leaves alone)
         G.kc[0] = (uint16_t)c0; G.kc[1] = (uint16_t)c1; G.kc[2] = (uint16_t)c2; G.kc[3] = (uint16_t)c3;
         G.mincov = (int)(c0 + c1 + c2 + c3); G.mincovqv = (int)X.c_minqv[ci];
+        if (try_settle) {                                            // the settled test (below), this survivor's share: only a node of the reference has one
+          const uint32_t p = st_own[si];
+          if (p != LC_NIL) {
+            const uint32_t bit = 1u << (p & 31u);
+            if ((float)(c0 + c1 + c2 + c3 + (rv & 0xFFFFu) + (rv >> 16)) >= (float)P->cov_threshold) {       // Q: markRefEnds' own predicate
+              if ((st_multi[si >> 5] >> (si & 31u)) & 1u) ST[0] = 1u;                                        // (in Q at two offsets: one of them is no run node's first)
+              else dev_atomic_or(&st_q[p >> 5], bit);
+            }
+            // the links of the pseudo-read's steps p -> p + 1 (this node is u) and p - 1 -> p (it is v) as the loop above resolves them, where the
+            // neighbour survives: the node's list has to be exactly these
+            const bool up = (int)p + 1 < nrefk && ((st_sb[(p + 1u) >> 5] >> ((p + 1u) & 31u)) & 1u), dn = p > 0u && ((st_sb[(p - 1u) >> 5] >> ((p - 1u) & 31u)) & 1u);
+            bool ok = (uint32_t)m == (up ? 1u : 0u) + (dn ? 1u : 0u);
+            if (ok && m > 0) {
+              const uint32_t rbS = 16u * S.rdo[nr];
+              const uint32_t e = X.occn[rbS + p], o = (e >> ON_ORISH) & 1u;
+              uint32_t w0 = 0, w1 = 0;
+              if (up) { const uint32_t e2 = X.occn[rbS + p + 1u], o2 = (e2 >> ON_ORISH) & 1u; w0 = ED_MAKE(e2 & ON_ID, o == 0 ? (o2 == 0 ? 0u : 1u) : (o2 == 0 ? 2u : 3u)); }
+              if (dn) { const uint32_t e0 = X.occn[rbS + p - 1u], o0 = (e0 >> ON_ORISH) & 1u; w1 = ED_MAKE(e0 & ON_ID, o0 == 0 ? (o == 0 ? 3u : 1u) : (o == 0 ? 2u : 0u)); }
+              if (m == 1) ok = ed0 == (up ? w0 : w1);
+              else ok = (ed0 == w0 && ed1 == w1) || (ed0 == w1 && ed1 == w0);
+            }
+            if (ok) dev_atomic_or(&st_ok[p >> 5], bit);
+          }
+        }
         const uint32_t base = ci * (uint32_t)K;
         G.seq_clo = base; G.seq_lo = base; G.seq_hi = base + (uint32_t)K; G.seq_chi = base + (uint32_t)K;
         G.nqv = ci;
@@ -2022,49 +2068,38 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
       WG_SYNC();
     }
   }
-  // ---- settled windows ("Settled windows"; layout.h PreHdr::settled): the survivors are the nodes of one run [a, b] of
-  //      reference offsets, each at one offset only, and every one's filtered edge list is exactly the two links (one at the ends of the run)
-  //      that the reference pseudo-read's own steps made.  Such a graph is one component without a cycle whose source -> sink paths all spell
-  //      the window reference: the window ends at this k with no record, whatever the coverages are, and nothing below is needed for it.
-  //      Two passes over the reference offsets; the words are the edge slots' area above, free again.
+  // ---- settled windows ("Settled windows"; layout.h PreHdr::settled).  Q: the reference offsets whose node survives with
+  //      getTotCov() >= COV_THRESHOLD (markRefEnds' own predicate); [a, b]: the maximal run of consecutive surviving offsets that holds min Q.
+  //      Settled iff every offset of the run is its node's first, every run node's filtered edge list is exactly the two links (one at the run's
+  //      ends) that the reference pseudo-read's own steps made -- the run is then a whole component, a chain -- and Q lies inside the run: every
+  //      other component is without a source, sets no flag and emits nothing, and the chain's source -> sink paths all spell the window
+  //      reference.  The window ends at this k with no record and nothing below is needed for it.  No Q at all: no component has a source,
+  //      settled whatever the graph.  C->settle == 2 (LANCET_SETTLE_CHAIN_ONLY): the rule before this one, the run has to be all the survivors.
+  //      The lanes that formed the records have said of every survivor's first offset whether its links are those of its run (st_ok) and
+  //      whether it is in Q (st_q); what is left is the run around min Q, read off the bitmaps -- the same words in every lane, nothing written.
   bool settled = false;
-  if (C->settle && !rep && K <= 31 && !(BL_WIDE != 0 && N > 4096u) && nsurv > 0 && !hasN && !P->lr_mode && C->debug_stop == 0u && !C->evt_cap && !C->hap_cap &&
-      reflen - K + 1 > 0 && reflen - K + 1 <= (int)LC_MAXW && nsurv <= (uint32_t)(reflen - K + 1)) {
-    static_assert(BL_BIG / 4u >= BL_NCAP / 32u + BL_NCAP / 4u + 4u + (uint32_t)LC_MAXW, "words of the settled test");
-    LC_LDS uint32_t *T = S.big + BL_NCAP / 32 + BL_NCAP / 4;       // [0] a, [1] b, [2] a rule is broken
-    LC_LDS uint32_t *own = T + 4;                                  // [nsurv] first reference offset of survivor si
-    LC_GLOBAL const NodeGr *pgr = (LC_GLOBAL const NodeGr *)(area + PRE_OFF_PGR);
-    const int nrefk = reflen - K + 1;
-    const uint32_t rb = 16u * S.rdo[nr];
-    WG_SYNC();
-    WG_LANE0 { T[0] = LC_NIL; T[1] = 0; T[2] = 0; }
-    WG_FOR(si, nsurv) { own[si] = LC_NIL; }
-    WG_SYNC();
-    WG_FOR(i, nrefk) {
-      const uint32_t si = S.cidx[X.occn[rb + (uint32_t)i] & ON_ID];
-      if (si != 0xFFFFu) { dev_atomic_min(&own[si], (uint32_t)i); dev_atomic_min(&T[0], (uint32_t)i); dev_atomic_max(&T[1], (uint32_t)i); }
+  if (try_settle) {
+    const uint32_t NWORD = (uint32_t)LC_MAXW / 32u;
+    auto first_bit = [&](LC_LDS const uint32_t *bm) -> uint32_t { for (uint32_t w = 0; w < NWORD; ++w) { const uint32_t m = bm[w]; if (m) return (w << 5) + (uint32_t)dev_popc((m & (0u - m)) - 1u); } return LC_NIL; };
+    auto top_of = [](uint32_t m) -> uint32_t { m |= m >> 1; m |= m >> 2; m |= m >> 4; m |= m >> 8; m |= m >> 16; return (uint32_t)dev_popc(m) - 1u; };      // (index of the highest set bit, m != 0)
+    auto last_bit = [&](LC_LDS const uint32_t *bm) -> uint32_t { for (uint32_t w = ((uint32_t)nrefk - 1u) >> 5; ; --w) { const uint32_t m = bm[w]; if (m) return (w << 5) + top_of(m); if (w == 0u) break; } return LC_NIL; };
+    const bool chain_only = C->settle == 2u;
+    const uint32_t q0 = chain_only ? first_bit(st_sb) : first_bit(st_q);
+    if (q0 == LC_NIL) settled = !chain_only && ST[0] == 0u;          // (no node for markRefEnds to take in any component)
+    else if (((st_ok[q0 >> 5] >> (q0 & 31u)) & 1u) && (chain_only || ST[0] == 0u)) {
+      // the run of st_ok around q0: up to the first offset that is not in it, down to the last; a survivor there is a run node with other links or not at its first offset
+      uint32_t wi = q0 >> 5, m = ~st_ok[wi] & (0xFFFFFFFFu << (q0 & 31u));
+      while (m == 0u && wi + 1u < NWORD) m = ~st_ok[++wi];
+      const uint32_t e1 = m ? (wi << 5) + (uint32_t)dev_popc((m & (0u - m)) - 1u) : (uint32_t)LC_MAXW;
+      wi = q0 >> 5; m = ~st_ok[wi] & ~(0xFFFFFFFFu << (q0 & 31u));
+      while (m == 0u && wi > 0u) m = ~st_ok[--wi];
+      const uint32_t a = m ? (wi << 5) + top_of(m) + 1u : 0u, b = e1 - 1u;
+      bool ok = !(e1 < (uint32_t)LC_MAXW && ((st_sb[e1 >> 5] >> (e1 & 31u)) & 1u)) && !(a > 0u && ((st_sb[(a - 1u) >> 5] >> ((a - 1u) & 31u)) & 1u));
+      if (chain_only) ok = ok && b - a + 1u == nsurv;               // (the run's nodes are all the survivors)
+      else ok = ok && last_bit(st_q) <= b;                          // Q inside the run
+      settled = ok;
     }
-    WG_SYNC();
-    const uint32_t a = bl_bcast(&T[0]), b = bl_bcast(&T[1]);
-    if (a != LC_NIL && b - a + 1u == nsurv) {                      // (with every offset of [a, b] a survivor's first: the run's nodes are all the survivors)
-      WG_FOR(i, nrefk) {
-        if ((uint32_t)i < a || (uint32_t)i > b) continue;
-        const uint32_t e = X.occn[rb + (uint32_t)i], si = S.cidx[e & ON_ID], o = (e >> ON_ORISH) & 1u;
-        bool ok = si != 0xFFFFu && own[si] == (uint32_t)i;
-        if (ok) {
-          uint32_t want[2] = {0u, 0u}; uint32_t nw = 0;              // the links of the steps i -> i + 1 (this node is u) and i - 1 -> i (it is v), as the edge pass resolves them
-          if ((uint32_t)i < b) { const uint32_t e2 = X.occn[rb + (uint32_t)i + 1u], o2 = (e2 >> ON_ORISH) & 1u; want[nw++] = ED_MAKE(e2 & ON_ID, o == 0 ? (o2 == 0 ? 0u : 1u) : (o2 == 0 ? 2u : 3u)); }
-          if ((uint32_t)i > a) { const uint32_t e0 = X.occn[rb + (uint32_t)i - 1u], o0 = (e0 >> ON_ORISH) & 1u; want[nw++] = ED_MAKE(e0 & ON_ID, o0 == 0 ? (o == 0 ? 3u : 1u) : (o == 0 ? 2u : 0u)); }
-          LC_GLOBAL const NodeGr &G = pgr[si];
-          if (G.necnt != nw) ok = false;
-          else if (nw == 1u) ok = G.edges[0] == want[0];
-          else if (nw == 2u) ok = (G.edges[0] == want[0] && G.edges[1] == want[1]) || (G.edges[0] == want[1] && G.edges[1] == want[0]);
-        }
-        if (!ok) T[2] = 1u;
-      }
-      WG_SYNC();
-      settled = bl_bcast(&T[2]) == 0u;
-    }
+    WG_SYNC();                                                     // (the words are the next phase's)
   }
   BLP(S, 15);
   BL_TAIL_PRIO_SET(BL_TAIL_PRIO);

@@ -295,6 +295,7 @@ struct lancet_engine {
   int n_ahead_built = 0, n_ahead_used = 0;
   int n_settled = 0;          // windows of the last run that the build kernel settled (PreHdr::settled)
   bool no_settle = false;     // LANCET_NO_SETTLE=1: EngineCaps::settle stays 0
+  bool settle_chain_only = false;      // LANCET_SETTLE_CHAIN_ONLY=1: EngineCaps::settle = 2, only windows whose survivors are all in the reference chain (A/B runs, bisecting)
   bool heavy_first = true;    // LANCET_NO_HEAVY_FIRST=1: windows in batch order
   int order_mode = 0;         // LANCET_ORDER=two: two classes only (see order_class)
   unsigned long long blphase[16] = {0};
@@ -456,6 +457,7 @@ int lancet_engine_create(const lancet_params *p, int device, lancet_engine **out
   e->phase_times = getenv("LANCET_PHASE_TIMES") != nullptr && atoi(getenv("LANCET_PHASE_TIMES")) != 0;      // per-phase tick accounting of both kernels (tools/quick_gpu.py ...): clock reads per phase and contended atomics per window otherwise
   e->dbg = getenv("LANCET_DEBUG") != nullptr; e->no_fat = getenv("LANCET_NO_FAT") != nullptr; e->no_early_rerun = getenv("LANCET_NO_EARLY_RERUN") != nullptr;
   e->no_settle = getenv("LANCET_NO_SETTLE") != nullptr && atoi(getenv("LANCET_NO_SETTLE")) != 0;
+  e->settle_chain_only = getenv("LANCET_SETTLE_CHAIN_ONLY") != nullptr && atoi(getenv("LANCET_SETTLE_CHAIN_ONLY")) != 0;
   e->no_large_build = getenv("LANCET_NO_LARGE_BUILD") != nullptr; e->heavy_first = getenv("LANCET_NO_HEAVY_FIRST") == nullptr;
   if (const char *s = getenv("LANCET_ORDER")) e->order_mode = strcmp(s, "two") == 0 ? 1 : 0;
   if (const char *s = getenv("LANCET_BUILD_SLOTS")) e->build_slots_env = std::max(1, atoi(s));
@@ -614,7 +616,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
   e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
-  e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? 1u : 0u;
+  e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
 static int lc_upload(lancet_engine *e, const lancet_window_batch *b, const lancet_packed_reads *pk) {
   if (!e || !b || b->n_windows < 0) return LANCET_E_ARG;

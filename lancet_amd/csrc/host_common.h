@@ -181,7 +181,8 @@ static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_
 #ifdef LANCET_WAVE_EMU
   c.hap_cap = lc_emu_hap_sink.cap;                            // (the engine sets it from lancet_engine_set_haplotypes)
   // settled windows: off unless the emulation is told otherwise, and then by the engine's rule (engine.hip lc_upload_caps: no trace, no capture, no linked reads)
-  { const char *sv = getenv("LANCET_EMU_SETTLE"); c.settle = (sv && atoi(sv) == 1 && !evt_cap && !c.hap_cap && !c.lr_mode) ? 1u : 0u; }
+  { const char *sv = getenv("LANCET_EMU_SETTLE"); const char *co = getenv("LANCET_SETTLE_CHAIN_ONLY");
+    c.settle = (sv && atoi(sv) == 1 && !evt_cap && !c.hap_cap && !c.lr_mode) ? ((co && atoi(co) != 0) ? 2u : 1u) : 0u; }
 #endif
   return c;
 }

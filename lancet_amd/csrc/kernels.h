@@ -5983,7 +5983,7 @@ DEV void process_window(Ctx &c, int w, int rq = -1) {
     if (wg_bcast(&S.overflow)) break;
     WG_LANE0 { S.prebuilt = 0; S.pre_order = 0; S.seq_lazy = 0; if (LC_CTX(c).OUT->svc) dev_atomic_add(&LC_CTX(c).OUT->svc->beat, 1u); }
     // A window the build kernel settled (layout.h PreHdr::settled): its first graph is the reference's own k-mers in one
-    // chain, which ends the loop here with no record.  Only the header's counts are taken; there is no trace to write (settling is off with it).
+    // chain, beside components without a source at most, which ends the loop here with no record.  Only the header's counts are taken; there is no trace to write (settling is off with it).
     if (rq < 0 && H0 && wg_uniform((int)(H0->status == PB_BUILT && H0->settled == 1u && H0->K == k))) {
       WG_LANE0 {
         const uint32_t N = H0->N;

@@ -132,7 +132,8 @@ struct EngineCaps {
                             re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
   uint32_t hap_cap;      /* haplotype capture: words of the window's buffer (DevOut::hap_out), 0 = off (lancet_engine_set_haplotypes) */
   uint32_t settle;       /* the build kernel may settle reference-only windows (PreHdr::settled): set by the engine when nothing is on that wants to
-                            see such a window's graph -- trace, haplotype capture, linked reads -- and LANCET_NO_SETTLE is not set */
+                            see such a window's graph -- trace, haplotype capture, linked reads -- and LANCET_NO_SETTLE is not set.  1: the reference chain beside components without a source
+                             ; 2: the chain has to be the whole graph (LANCET_SETTLE_CHAIN_ONLY=1) */
   struct PreLayout pl;   /* hand-off areas of the LDS build kernel (below)                           */
 };
 
@@ -239,7 +240,7 @@ struct PreHdr {
                                  barcodes and haplotypes over them (kernels.h load_prebuilt_lr) instead of building the window in HBM    */
   uint32_t lr_total;          /* ... csr entries                                                                    */
   uint32_t hasN;              /* the window reference holds an N (valid with have_rep): the general build of a later k needs to know */
-  uint32_t settled;           /* the graph after the first removeLowCov is the reference's own k-mers in one chain and nothing else: the window ends at
+  uint32_t settled;           /* the graph after the first removeLowCov is the reference's own k-mers in one chain, beside components without a source at most: the window ends at
                                  this k with no record ("Settled windows").  Only the header's counts are valid: no table order, no
                                  components, no compress came along, and the window kernel loads nothing (EngineCaps::settle) */
   uint32_t pad[5];
