@@ -345,6 +345,26 @@ int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **
 /* Milliseconds on the host clock that the last run's read-back of the haplotypes took (the windows' lengths, the gather of the used words
  * on the device, one copy, the records); 0 with the capture off. */
 float lancet_engine_haplotype_readback_ms(const lancet_engine *e);
+/* ---- ... and how each lies on its reference stretch ----
+ * lancet_engine_set_haplotype_alignments(e, 1): the uploads that follow also keep every path's alignment to its stretch, the one the
+ * kernel walked for the records (global_align_aff's, or the two strings column by column for a path of the Hamming short-cut), as CIGAR
+ * words: length << 4 | op, BAM's op codes (LANCET_HAP_OP_*), one word per maximal run of columns -- neighbouring words differ in op,
+ * no length is 0, the I / = / X lengths sum to len and the D / = / X lengths to ref_len.  A haplotype identical to its stretch has one
+ * '=' run; LANCET_HAP_UNALIGNED ones have '=' and 'X' only.  on is 0 or 1 (else LANCET_E_ARG); the state rules are those of
+ * lancet_engine_set_haplotypes; without the capture itself the switch does nothing.  The words come out of the window's
+ * words_per_window: an entry of the window's buffer is LANCET_HAP_HEADER_WORDS header words, the (len + 15) / 16 path words, and the
+ * CIGAR words, whose number is header word LANCET_HAP_W_NCIGAR (0 with the switch off: the entry is then what it was before the switch
+ * existed).  A haplotype whose CIGAR does not fit is one that does not fit: truncated[w] = 1, the ones in front of it stay whole.
+ * lancet_engine_results_haplotype_alignments: after a run, the words of haplotype i of lancet_engine_results_haplotypes are
+ * cigar[cigar_off[i] .. cigar_off[i + 1]); with the switch off every offset is 0 and n_cigar is 0.  words / word_off / n_words of
+ * lancet_engine_results_haplotypes are path words only, whatever the switch says. */
+#define LANCET_HAP_W_NCIGAR 7
+#define LANCET_HAP_OP_I 1u        /* column with '-' in the reference string: bases of the path the stretch does not have */
+#define LANCET_HAP_OP_D 2u        /* column with '-' in the path string                                                   */
+#define LANCET_HAP_OP_EQ 7u       /* the same base in both                                                                */
+#define LANCET_HAP_OP_X 8u        /* another base (an N of the reference included)                                        */
+int lancet_engine_set_haplotype_alignments(lancet_engine *e, int on);
+int lancet_engine_results_haplotype_alignments(lancet_engine *e, const uint32_t **cigar_off /* [n + 1] */, const uint32_t **cigar, uint32_t *n_cigar);
 
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */

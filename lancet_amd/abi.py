@@ -101,6 +101,13 @@ class LancetHaplotype(C.Structure):
 
 HAP_HEADER_WORDS = 8          # LANCET_HAP_HEADER_WORDS: a haplotype of n bases takes this + (n + 15) // 16 words of its window's buffer
 HAP_UNALIGNED, HAP_IS_REF = 1, 2
+HAP_W_NCIGAR = 7              # LANCET_HAP_W_NCIGAR: the header word that counts an entry's CIGAR words (lancet_engine_set_haplotype_alignments)
+HAP_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}      # LANCET_HAP_OP_*: BAM's codes, SAM's extended letters
+
+
+def cigar_to_py(words) -> List[tuple]:
+    """CIGAR words (length << 4 | op) as (length, op_char) pairs."""
+    return [(int(w) >> 4, HAP_OPS[int(w) & 15]) for w in words]
 
 
 def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:

@@ -332,6 +332,7 @@ struct lancet_engine {
   // haplotype capture (lancet_engine_set_haplotypes): words per window of the next upload (0 = off; EngineCaps::hap_cap is what the uploaded batch has),
   // the windows' length words and buffers, the prefix sums and the dense copy of the read-back, the last run's result and what its read-back took
   uint32_t hap_words = 0;
+  uint32_t hap_aln = 0;       // lancet_engine_set_haplotype_alignments: the next upload's entries carry their CIGAR words (EngineCaps::hap_aln)
   DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
   LcHapResult hap;
   float ms_hap = 0;
@@ -541,6 +542,16 @@ int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window) {
   return LANCET_OK;
 }
 
+// ... and whether their entries carry the path's alignment to its reference stretch.  Same rules: laid out by an upload.
+int lancet_engine_set_haplotype_alignments(lancet_engine *e, int on) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotype_alignments while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotype_alignments between an upload and its run"; return LANCET_E_STATE; }
+  if (on != 0 && on != 1) { e->err = "set_haplotype_alignments: on is 0 or 1"; return LANCET_E_ARG; }
+  e->hap_aln = (uint32_t)on;
+  return LANCET_OK;
+}
+
 static int up(lancet_engine *e, DevBuf &b, const void *src, size_t bytes) {
   if (b.ensure(bytes ? bytes : 1)) { e->err = "hipMalloc failed"; return LANCET_E_OOM; }
   if (bytes) HIPCHK(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
@@ -615,6 +626,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   }
   e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
   e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
+  e->caps.hap_aln = e->caps2.hap_aln = e->hap_words ? e->hap_aln : 0u;
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
   e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
@@ -1252,6 +1264,7 @@ int lancet_engine_submit(lancet_engine *e) {
   e->ran = false;
   e->variants.clear(); e->blob.clear(); e->stats.clear(); e->evt_len.clear(); e->evt.clear(); e->variants_lr.clear(); e->bx_blob.clear();
   e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
+  e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear();
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1491,6 +1504,15 @@ int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **
   if (words) *words = e->hap.words.data();
   if (n_words) *n_words = (uint32_t)e->hap.words.size();
   if (truncated) *truncated = e->hap.truncated.data();
+  return LANCET_OK;
+}
+int lancet_engine_results_haplotype_alignments(lancet_engine *e, const uint32_t **cigar_off, const uint32_t **cigar, uint32_t *n_cigar) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  if (e->hap.cigar_off.size() != e->hap.h.size() + 1) e->hap.cigar_off.assign(e->hap.h.size() + 1, (uint32_t)e->hap.cigar.size());
+  if (cigar_off) *cigar_off = e->hap.cigar_off.data();
+  if (cigar) *cigar = e->hap.cigar.data();
+  if (n_cigar) *n_cigar = (uint32_t)e->hap.cigar.size();
   return LANCET_OK;
 }
 // milliseconds the last run's read-back of the haplotypes took on the host clock (lengths, compaction, copy, parsing); 0 with the capture off

@@ -5399,8 +5399,75 @@ DEVNI void hap_open(Ctx &c, int m, int hd, bool need_align) {
     p[HP_W_REFOFF] = (uint32_t)S.seq_t5; p[HP_W_REFLEN] = (uint32_t)S.seq_len; p[HP_W_LEN] = (uint32_t)m;
     p[HP_W_FIRST] = (uint32_t)S.emit_seq; p[HP_W_NVAR] = 0;
     p[HP_W_FLAGS] = (need_align ? 0u : LANCET_HAP_UNALIGNED) | (hd == 0 ? LANCET_HAP_IS_REF : 0u);
-    p[7] = 0;
+    p[HP_W_NCIG] = 0;
   }
+}
+// ... and how it lies on the reference stretch (EngineCaps::hap_aln), behind the path words of the entry hap_open wrote: one word
+// length << 4 | HP_OP_* per maximal run of alignment columns of one class, the four classes of printVerticalAlignment (reference
+// src/Graph.cc:761-764).  Once per path, when its alignment is known and before anything walks it.  m: bases of the path string.
+//   hd == 0: the path spells the stretch -- one '=' run.
+//   0 < hd <= LC_HD_MAX: no alignment was made; the mismatch positions are in S.part2 as the lanes met them.  Lane 0 sorts them (the
+//     walk's own sort then finds them in order) and writes the '=' runs between them, neighbouring mismatches as one 'X' run.
+//   otherwise: the L columns of the two strings in W.aln.  A column starts a run when its class is not its left neighbour's; an exclusive
+//     scan of the start flags numbers the runs in column order, every start notes its column under its number, and run r is as long as
+//     the distance to the next start.  W.scratch holds flags and starts: the traceback's notes are used up, walk_prepare writes it anew.
+// Words that do not fit mark the window HP_TRUNC, as a path string that does not fit: hap_close then leaves the entry uncounted.
+DEV uint32_t hap_col_op(uint8_t r, uint8_t p) { return r == p ? (uint32_t)HP_OP_EQ : (r == '-' ? (uint32_t)HP_OP_I : (p == '-' ? (uint32_t)HP_OP_D : (uint32_t)HP_OP_X)); }
+DEVNI void hap_cigar(Ctx &c, int m, int hd, int L) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const uint32_t cap = LC_CTX(c).C->hap_cap;
+  const int w = wg_uniform(S.w);
+  LC_GLOBAL uint32_t *lenp = LC_HAP_LEN(c) + w;
+  const uint32_t cur = (uint32_t)wg_uniform((int)ld2(lenp));
+  WG_SYNC();                                                               // (every wave has read the word before lane 0 may mark it)
+  if (cur & HP_TRUNC) return;
+  const uint32_t used = cur + HP_HDR + ((uint32_t)m + 15u) / 16u;          // (hap_open found room for these)
+  LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)w * cap + cur;
+  LC_GLOBAL uint32_t *q = LC_HAP_OUT(c) + (size_t)w * cap + used;
+  const uint32_t room = cap - used;
+  if (hd >= 0 && hd <= LC_HD_MAX) {
+    WG_LANE0 {
+      for (int a = 1; a < hd; ++a) {
+        const uint32_t v = S.part2[a]; int b = a;
+        for (; b > 0 && S.part2[b - 1] > v; --b) S.part2[b] = S.part2[b - 1];
+        S.part2[b] = v;
+      }
+      uint32_t n = 1;                                                      // words: an '=' run where the mismatch runs leave a gap
+      for (int a = 0; a < hd; ++a) {
+        const uint32_t i = S.part2[a];
+        if (a == 0) n = i > 0 ? 1u : 0u;
+        if (a == 0 || S.part2[a - 1] + 1u != i) n += 1u;
+        if (i + 1u < (uint32_t)m && (a + 1 == hd || S.part2[a + 1] != i + 1u)) n += 1u;
+      }
+      if (n > room) st2(lenp, cur | HP_TRUNC);
+      else {
+        uint32_t k = 0, at = 0;                                            // at: first column not yet in a run
+        for (int a = 0; a < hd;) {
+          const uint32_t i = S.part2[a];
+          int b = a + 1;
+          while (b < hd && S.part2[b] == S.part2[b - 1] + 1u) ++b;
+          if (i > at) q[k++] = ((i - at) << 4) | (uint32_t)HP_OP_EQ;
+          q[k++] = ((uint32_t)(b - a) << 4) | (uint32_t)HP_OP_X;
+          at = i + (uint32_t)(b - a); a = b;
+        }
+        if ((uint32_t)m > at) q[k++] = (((uint32_t)m - at) << 4) | (uint32_t)HP_OP_EQ;
+        p[HP_W_NCIG] = k;
+      }
+    }
+    return;
+  }
+  const int acap = (int)LC_CTX(c).C->max_w + (int)LC_CTX(c).C->path_cap + 2;
+  LC_GLOBAL const uint8_t *ra = W.aln, *pa = W.aln + acap;
+  LC_GLOBAL uint32_t *F = W.scratch, *pos = W.scratch + (L + 1);
+  WG_FOR(i, L) { F[i] = (i == 0 || hap_col_op(ra[i], pa[i]) != hap_col_op(ra[i - 1], pa[i - 1])) ? 1u : 0u; }
+  WG_LANE0 { F[L] = 0; }
+  wg_scan(F, L + 1, S, S.part2);
+  const uint32_t nr = (uint32_t)wg_uniform((int)S.part2[LANCET_WG]);
+  if (nr > room) { WG_LANE0 { st2(lenp, cur | HP_TRUNC); } return; }
+  WG_FOR(i, L) { if (F[i + 1] != F[i]) pos[F[i]] = (uint32_t)i; }
+  WG_LANE0 { pos[nr] = (uint32_t)L; p[HP_W_NCIG] = nr; }
+  WG_FOR(r, nr) { const uint32_t s = pos[r]; q[r] = ((pos[r + 1] - s) << 4) | hap_col_op(ra[s], pa[s]); }
+  WG_SYNC();
 }
 // lane 0, after the path's walk: the records it emitted, and the entry counts
 DEV void hap_close(Ctx &c) {
@@ -5411,7 +5478,7 @@ DEV void hap_close(Ctx &c) {
   if (cur & HP_TRUNC) return;
   LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)S.w * cap + cur;
   p[HP_W_NVAR] = (uint32_t)S.emit_seq - p[HP_W_FIRST];
-  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u);
+  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG]);
 }
 
 // eka (reference src/Graph.cc:1430-1501) via countRefPath (:2420-2445)
@@ -5419,6 +5486,7 @@ DEVNI void count_ref_path(Ctx &c) {
   LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
   if (wg_bcastu(&S.source) == LC_NIL) return;
   const bool hap_on = wg_uniform((int)LC_CTX(c).C->hap_cap) != 0;      // (haplotype capture: the one test of a run without it)
+  const bool hap_aln = hap_on && wg_uniform((int)LC_CTX(c).C->hap_aln) != 0;      // (... with the CIGARs: read with the capture on only)
   if (wg_bcastu(&S.sink) != LC_NIL) {
     WG_LANE0 { evt(c, EV_SEARCH, (uint32_t)W.gr[S.source].comp); S.tmp0 = S.tmp1 = S.tmp2 = 0; S.part[0] = 0; S.part[1] = 0; S.part[2] = 0; S.part[3] = 0; S.pc_i = 0; S.pc_rd = 0; }
     const bool replay = wg_bcast(&S.pc_ok) != 0;             // the paths are the ones findRepeatsInGraphPaths found (pcache_store)
@@ -5498,6 +5566,8 @@ DEVNI void count_ref_path(Ctx &c) {
         WG_SYNC();
         align_traceback_fill(c, rs, W.pseq, (int)wg_bcastu(&S.part[7]));
       }
+      // ... and its CIGAR, now that the alignment is known: before the walk, so that a path the wave driver hands to the one-lane driver has one
+      if (hap_aln && !wg_bcast(&S.overflow)) hap_cigar(c, (int)wg_bcastu(&S.part[5]), hd, (int)wg_bcastu(&S.part[7]));
       PHASE(c, 14);
       if (hd == 0 && !old_walk) {
         SUBPHASE(c, 4, 7);

@@ -28,6 +28,11 @@
 // the path was compared with; variants: the window's records, in emission order, that this path emitted).  The buffer is sized per batch
 // (hap_words_for); windows whose haplotypes did not all fit are counted on stderr.  Not with --ranks above 1 (the gather carries records only);
 // the option is left out of ##cmdline: the VCF is byte for byte the one without it.
+// --haplotype-sam FILE: the same haplotypes as SAM records, each aligned to the contig as the window kernel aligned it to its reference stretch
+// (lancet_engine_set_haplotype_alignments): @HD / @SQ per contig of the FASTA / @PG, then per haplotype QNAME = the FASTA record's name up to
+// path=.., FLAG 0, POS = first base of the stretch, MAPQ 255, the CIGAR in = X I D (a D run at either end is dropped, POS moves past a leading
+// one), SEQ, and the tags kk:i (k) cp:i (component) pi:i (index in window) wn:Z (window) vf:i / vn:i (first_variant, n_variants) fl:i (flags).
+// Alone or with --haplotypes; the same rules (not with --ranks above 1, left out of ##cmdline); the buffer is 64 words per path larger.
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
 
@@ -36,6 +41,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +50,7 @@
 #include <future>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -58,7 +65,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -71,6 +78,37 @@ uint32_t trace_words_for(uint32_t longest, int max_indel_len) {
 // --haplotypes: words per window of such a batch: MV_PATHS haplotypes of up to longest + --max-indel-len + 256 bases, 16 bases to a word behind a header
 uint32_t hap_words_for(uint32_t longest, int max_indel_len) {
   return MV_PATHS * ((uint32_t)LANCET_HAP_HEADER_WORDS + (longest + (uint32_t)max_indel_len + 256u + 15u) / 16u);
+}
+// --haplotype-sam: 64 more words per path for the runs of its CIGAR
+uint32_t hap_cigar_words() { return MV_PATHS * 64u; }
+// --haplotype-sam: (name, length) of the contigs of a FASTA file in its order -- from its .fai when there is one, else from the file itself
+bool fasta_contigs(const std::string &path, std::vector<std::pair<std::string, long>> *out) {
+  out->clear();
+  if (FILE *f = fopen((path + ".fai").c_str(), "r")) {
+    char line[4096];
+    while (fgets(line, sizeof line, f)) {
+      char *t1 = strchr(line, '\t');
+      if (!t1) continue;
+      out->emplace_back(std::string(line, (size_t)(t1 - line)), atol(t1 + 1));
+    }
+    fclose(f);
+    if (!out->empty()) return true;
+  }
+  FILE *f = fopen(path.c_str(), "r");
+  if (!f) return false;
+  std::vector<char> buf(1 << 16);
+  bool bol = true, in_name = false, in_head = false;
+  size_t n;
+  while ((n = fread(buf.data(), 1, buf.size(), f)) > 0) for (size_t i = 0; i < n; ++i) {
+    const char ch = buf[i];
+    if (ch == '\n') { bol = true; in_name = in_head = false; continue; }
+    if (bol && ch == '>') { out->emplace_back(std::string(), 0L); in_name = in_head = true; bol = false; continue; }
+    bol = false;
+    if (in_head) { if (in_name && !isspace((unsigned char)ch)) out->back().first += ch; else in_name = false; }
+    else if (!out->empty() && ch != '\r') ++out->back().second;
+  }
+  fclose(f);
+  return true;
 }
 int die(const std::string &m) { fprintf(stderr, "lancet_gpu: %s\n", m.c_str()); return 1; }
 void usage() {
@@ -97,6 +135,8 @@ void usage() {
         "                                       graph by a window without mapped reads, oversize windows -- go the usual way; same VCF either way\n"
         "   --haplotypes <file>               : every assembled path of every window as FASTA (>chr:start-end|k=|comp=|path=|ref=off+len|variants=first+n),\n"
         "                                       at full throughput; same VCF, the option is left out of ##cmdline; not with --ranks above 1\n"
+        "   --haplotype-sam <file>            : the same haplotypes as SAM records on the contig, CIGAR in = X I D as the window kernel aligned them;\n"
+        "                                       alone or with --haplotypes, same rules\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -111,7 +151,7 @@ int main(int argc, char **argv) {
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
-  std::string rendezvous, hap_file;
+  std::string rendezvous, hap_file, sam_file;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -141,7 +181,7 @@ int main(int argc, char **argv) {
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
-    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v;
+    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -149,6 +189,7 @@ int main(int argc, char **argv) {
   if (kmer_recovery && ho.linked) return die("--kmer-recovery (-R) is not supported together with --linked-reads: the linked-read coverages come out of the barcode replay, where recovery is not built");
   if (ranks < 0 || (ranks == 0 && rank >= 0) || (ranks > 0 && rank >= ranks)) return die("--ranks must be >= 1 and --rank one of 0 .. ranks-1");
   if (!hap_file.empty() && ranks > 1) return die("--haplotypes is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (!sam_file.empty() && ranks > 1) return die("--haplotype-sam is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -254,9 +295,20 @@ int main(int argc, char **argv) {
   }
   FILE *hap_out = nullptr;
   if (!hap_file.empty() && !(hap_out = fopen(hap_file.c_str(), "w"))) return die("cannot write " + hap_file);
-  const bool hap_on = hap_out != nullptr;
+  FILE *sam_out = nullptr;
+  if (!sam_file.empty()) {
+    std::vector<std::pair<std::string, long>> contigs;
+    if (!fasta_contigs(ref, &contigs)) return die("cannot read " + ref);
+    if (!(sam_out = fopen(sam_file.c_str(), "w"))) return die("cannot write " + sam_file);
+    fputs("@HD\tVN:1.6\tSO:unsorted\n", sam_out);
+    for (const auto &ct : contigs) fprintf(sam_out, "@SQ\tSN:%s\tLN:%ld\n", ct.first.c_str(), ct.second);
+    fputs("@PG\tID:lancet_gpu\tPN:lancet_gpu\n", sam_out);
+  }
+  const bool sam_on = sam_out != nullptr;
+  const bool hap_on = hap_out != nullptr || sam_on;      // either file turns the capture on; the SAM one the alignments as well
+  const uint32_t hap_extra = sam_on ? hap_cigar_words() : 0u;
   long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
-  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
@@ -309,18 +361,44 @@ int main(int argc, char **argv) {
     if (hap_on) {
       const lancet_haplotype *hp; uint32_t nh = 0, nwords = 0; const uint32_t *words; const uint8_t *trunc;
       if (lancet_engine_results_haplotypes(sl.e, &hp, &nh, &words, &nwords, &trunc) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+      const uint32_t *cig_off = nullptr, *cig = nullptr; uint32_t ncig = 0;
+      if (sam_on && lancet_engine_results_haplotype_alignments(sl.e, &cig_off, &cig, &ncig) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
       for (uint32_t i = 0; i < nh; ++i) {
         const lancet_haplotype &x = hp[i];
         if (x.window < 0 || x.window >= sl.nk || (uint64_t)x.word_off + (x.len + 15u) / 16u > nwords) continue;
+        const int tw = sl.kept[(size_t)x.window];
+        const char *hdr = lancet_host_window_hdr(H, tw);
         char head[256];
-        snprintf(head, sizeof head, ">%s|k=%u|comp=%u|path=%d|ref=%u+%u|variants=%d+%d\n", lancet_host_window_hdr(H, sl.kept[(size_t)x.window]), (unsigned)x.kmer, (unsigned)x.component,
-                 x.index_in_window, x.ref_off, x.ref_len, x.first_variant, x.n_variants);
-        j.hapfa += head;
-        const size_t at = j.hapfa.size();
-        j.hapfa.resize(at + x.len + 1);
-        for (uint32_t b = 0; b < x.len; ++b) j.hapfa[at + b] = "ACGT"[(words[x.word_off + b / 16u] >> (2u * (b % 16u))) & 3u];
-        j.hapfa[at + x.len] = '\n';
+        std::string seq((size_t)x.len, 'A');
+        for (uint32_t b = 0; b < x.len; ++b) seq[b] = "ACGT"[(words[x.word_off + b / 16u] >> (2u * (b % 16u))) & 3u];
+        if (hap_out) {
+          snprintf(head, sizeof head, ">%s|k=%u|comp=%u|path=%d|ref=%u+%u|variants=%d+%d\n", hdr, (unsigned)x.kmer, (unsigned)x.component,
+                   x.index_in_window, x.ref_off, x.ref_len, x.first_variant, x.n_variants);
+          j.hapfa += head; j.hapfa += seq; j.hapfa += '\n';
+        }
+        if (sam_on) {
+          // the engine's runs; a D run at either end is no part of a read's alignment, and POS moves past a leading one
+          uint32_t c0 = cig_off[i], c1 = cig_off[i + 1];
+          if (c1 > ncig || c0 > c1) continue;
+          int32_t start = 0, end = 0; lancet_host_window_span(H, tw, &start, &end);
+          long pos = (long)start + (long)x.ref_off;      // 1-based: a record of the window sits at pos + 1 - this in the stretch (0-based pos)
+          if (c0 < c1 && (cig[c0] & 15u) == LANCET_HAP_OP_D) { pos += (long)(cig[c0] >> 4); ++c0; }
+          if (c0 < c1 && (cig[c1 - 1] & 15u) == LANCET_HAP_OP_D) --c1;
+          snprintf(head, sizeof head, "%s|k=%u|comp=%u|path=%d\t0\t%s\t%ld\t255\t", hdr, (unsigned)x.kmer, (unsigned)x.component, x.index_in_window,
+                   chr_names[lancet_host_window_chrom(H, tw)], pos);
+          j.hapsam += head;
+          if (c0 == c1) j.hapsam += '*';
+          for (uint32_t q = c0; q < c1; ++q) {
+            const uint32_t op = cig[q] & 15u;
+            j.hapsam += std::to_string(cig[q] >> 4);
+            j.hapsam += op == LANCET_HAP_OP_EQ ? '=' : op == LANCET_HAP_OP_X ? 'X' : op == LANCET_HAP_OP_I ? 'I' : 'D';
+          }
+          j.hapsam += "\t*\t0\t0\t"; j.hapsam += seq;
+          snprintf(head, sizeof head, "\t*\tkk:i:%u\tcp:i:%u\tpi:i:%d\twn:Z:%s\tvf:i:%d\tvn:i:%d\tfl:i:%u\n", (unsigned)x.kmer, (unsigned)x.component, x.index_in_window, hdr,
+                   x.first_variant, x.n_variants, x.flags);
+          j.hapsam += head;
+        }
         ++n_hap;
       }
     }
@@ -333,6 +411,7 @@ int main(int argc, char **argv) {
       Job &j = jobs[(size_t)next_add];
       if (!j.trace.empty()) fputs(j.trace.c_str(), stderr);
       if (!j.hapfa.empty() && fwrite(j.hapfa.data(), 1, j.hapfa.size(), hap_out) != j.hapfa.size()) { fail = "cannot write " + hap_file; return false; }
+      if (!j.hapsam.empty() && fwrite(j.hapsam.data(), 1, j.hapsam.size(), sam_out) != j.hapsam.size()) { fail = "cannot write " + sam_file; return false; }
       int arc = LANCET_OK;
       if (ranked) {                                  // the records travel: keyed, reduced, window numbers of the whole tiling
         if (!j.v.empty()) {
@@ -404,7 +483,8 @@ int main(int argc, char **argv) {
           uint32_t longest = 0;
           for (int32_t i = 0; i < SL.n_windows; ++i) longest = std::max(longest, SL.ref_off[i + 1] - SL.ref_off[i]);
           if (more_verbose && lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
-          if (hap_on && lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+          if (hap_on && (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, sam_on ? 1 : 0) != LANCET_OK))
+            return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
         }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
         t_engine += now() - t0; t0 = now();
@@ -435,7 +515,8 @@ int main(int argc, char **argv) {
     if (!taken && hap_on) {
       uint32_t longest = 0;
       for (int32_t w = 0; w < nk; ++w) longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]);
-      if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+      if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, sam_on ? 1 : 0) != LANCET_OK)
+        return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     t_engine += now() - t0;
@@ -466,10 +547,16 @@ int main(int argc, char **argv) {
   if (more_verbose && n_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose -V trace did not fit its buffer (%u paths of the longest window reference + --max-indel-len bases): their text ends with a [trace truncated] line%s\n",
                                            n_truncated, MV_PATHS, ranked ? (" [rank " + std::to_string(rank) + "]").c_str() : "");
   if (hap_on) {
-    if (fclose(hap_out) != 0) return die("cannot write " + hap_file);
-    fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, hap_file.c_str());
+    if (hap_out) {
+      if (fclose(hap_out) != 0) return die("cannot write " + hap_file);
+      fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, hap_file.c_str());
+    }
+    if (sam_on) {
+      if (fclose(sam_out) != 0) return die("cannot write " + sam_file);
+      fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, sam_file.c_str());
+    }
     if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
-                                 n_hap_truncated, MV_PATHS, hap_file.c_str());
+                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_file.c_str());
   }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
@@ -516,7 +603,7 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
-    if (strcmp(argv[i], "--haplotypes") == 0) { ++i; continue; }  // (a second output of the same run)
+    if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

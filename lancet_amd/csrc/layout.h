@@ -131,6 +131,7 @@ struct EngineCaps {
   uint32_t todo_cap;     /* occurrences the mate-overlap prefilter may flag: table_cap in tier 1 (todo[] doubles as the slot -> node table), in the
                             re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
   uint32_t hap_cap;      /* haplotype capture: words of the window's buffer (DevOut::hap_out), 0 = off (lancet_engine_set_haplotypes) */
+  uint32_t hap_aln;      /* ... with every entry's CIGAR words behind its path words (lancet_engine_set_haplotype_alignments); read only where hap_cap != 0 */
   uint32_t settle;       /* the build kernel may settle reference-only windows (PreHdr::settled): set by the engine when nothing is on that wants to
                             see such a window's graph -- trace, haplotype capture, linked reads -- and LANCET_NO_SETTLE is not set.  1: the reference chain beside components without a source
                              ; 2: the chain has to be the whole graph (LANCET_SETTLE_CHAIN_ONLY=1) */
@@ -138,7 +139,9 @@ struct EngineCaps {
 };
 
 /* ---- haplotype capture: one buffer of EngineCaps::hap_cap words per window, entries one behind the other in processPath order ----
- * An entry is HP_HDR header words and the path string behind them, 16 bases to a word (2 bits per base, first base in the low bits).
+ * An entry is HP_HDR header words and the path string behind them, 16 bases to a word (2 bits per base, first base in the low bits);
+ * with EngineCaps::hap_aln the path's alignment to the reference stretch follows, header word HP_W_NCIG words of length << 4 | op, one per
+ * maximal run of columns of one class (HP_OP_*: BAM's codes; kernels.h hap_cigar).  Without it that word is 0 and nothing follows.
  * DevOut::hap_len[w] holds the words of the window's CLOSED entries: the entry of the path being walked lies behind them and counts
  * once its walk is through (kernels.h hap_open / hap_close).  HP_TRUNC in that word: an entry did not fit, nothing is written after it. */
 #define HP_HDR 8u
@@ -147,7 +150,11 @@ enum { HP_W_KC = 0,        /* k | component << 16                               
        HP_W_REFOFF, HP_W_REFLEN,   /* Ref_t::seq as (offset into the window reference, length)         */
        HP_W_LEN,           /* bases of the path string                                                 */
        HP_W_FIRST, HP_W_NVAR,      /* seq_in_window of the path's first record, number of its records  */
-       HP_W_FLAGS };       /* LANCET_HAP_* ; word 7 is 0                                               */
+       HP_W_FLAGS,         /* LANCET_HAP_*                                                             */
+       HP_W_NCIG };        /* = 7: CIGAR words behind the path words (0 without EngineCaps::hap_aln)   */
+enum { HP_OP_I = 1,        /* column with '-' in the reference string                                  */
+       HP_OP_D = 2,        /* column with '-' in the path string                                       */
+       HP_OP_EQ = 7, HP_OP_X = 8 };   /* both strings have a base: the same / another                  */
 
 /* device-resident batch (after upload + prep) */
 struct DevBatch {
@@ -411,8 +418,8 @@ struct DevOut {
 /* Host emulation of the kernels only: where the haplotype capture writes and how large a window's buffer is.  The emulator's driver
  * fills a DevOut of its own; a test build that wants the capture sets this before the run (tests/hap_emu), lc_caps_for_sizes and the
  * kernels read it in place of DevOut::hap_len / hap_out. */
-struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; };
-inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr};
+struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; uint32_t aln; /* EngineCaps::hap_aln of the run */ };
+inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr, 0u};
 #define LC_HAP_LEN(c) (lc_emu_hap_sink.len)
 #define LC_HAP_OUT(c) (lc_emu_hap_sink.out)
 #else
