@@ -71,6 +71,7 @@ struct BlScratch {
 static constexpr uint32_t BL_PQCAP = 16384u;
 static constexpr uint32_t BL_NMW = LC_MAXW / 32;    /* words of the N mask of a window reference (one bit per base) */
 static constexpr uint32_t SCRATCH_BYTES = (((uint32_t)sizeof(bl_on_t) * BL_BASES + 64u + (BL_WIDE ? 4u * BL_NCAP + 64u : 64u) + 8u * BL_TCAP + 4u * BL_TCAP + 12u * PB_CCAP + 4u * PB_SCAP + 36u * PB_SCAP + (uint32_t)sizeof(bl_off_t) * BL_DUPCAP + 16u * PB_CMAX + 4u * 16384u + 768u) + 255u) & ~255u;   /* (a multiple of 256: the strips' 16-byte loads stay aligned in every slot) */
+static constexpr uint32_t ST_FIXED = 4u + 3u * ((uint32_t)LC_MAXW / 32u) + PB_SCAP / 32u;   /* words of the settled test in front of st_own (bl_build_window) */
 static constexpr int WG = BL_WG;
 DEV void bl_scratch_carve(BlScratch *s, LC_GLOBAL uint8_t *base) {
   size_t o = 0;
@@ -1851,7 +1852,6 @@ DEVNI void bl_build_window(LC_GLOBAL const lancet_params *P, LC_GLOBAL const Dev
   LC_LDS uint32_t *st_q = st_ok + LC_MAXW / 32;                    // ... its node has getTotCov() >= COV_THRESHOLD (a node at one offset only; at several: ST[0])
   LC_LDS uint32_t *st_multi = st_q + LC_MAXW / 32;                 // [PB_SCAP / 32] bit si: survivor si is at more than one reference offset
   LC_LDS uint32_t *st_own = st_multi + PB_SCAP / 32;               // [nsurv] first reference offset of survivor si
-  constexpr uint32_t ST_FIXED = 4u + 3u * ((uint32_t)LC_MAXW / 32u) + PB_SCAP / 32u;
   static_assert(BL_NCAP / 4u > ST_FIXED + 512u, "words of the settled test");
   const bool try_settle = C->settle && !rep && K <= 31 && !(BL_WIDE != 0 && N > 4096u) && nsurv > 0 && nsurv <= PB_SCAP && nsurv <= BL_NCAP / 4u - ST_FIXED && !hasN &&
                           !P->lr_mode && C->debug_stop == 0u && !C->evt_cap && !C->hap_cap && reflen - K > 0 && reflen - K + 1 <= (int)LC_MAXW;      // (a reference of more than K bases: it has k-mers, nrefk of them)

@@ -18,6 +18,8 @@ import hap_emu  # noqa: E402
 
 _LIBS = {}
 LAST_SETTLED = []            # windows of the last run that the build kernel settled
+LAST_WHY = []                # per window of the last run: why the build kernel turned it away (build_lds.h BLW_*), 0 where it built it
+LIMIT_NAMES = ("gmax", "cap", "st_fixed", "scap", "ccap", "ncap", "maxw", "rmax", "qvcap", "qvcap_wide", "wide_table_from")
 
 
 def lib():
@@ -34,8 +36,19 @@ def lib():
             hap_emu._LIBS.clear()
             hap_emu._LIBS.update(saved)
         L.lancet_settle_emu_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.lancet_settle_emu_why.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.lancet_settle_emu_limits.argtypes = [C.c_int, C.c_void_p, C.c_int]
         _LIBS[fat] = L
     return _LIBS[fat]
+
+
+def limits(large: bool = False):
+    """The sizes the settled test is written for, as the headers have them (emu_settle.cc lancet_settle_emu_limits): a dict over LIMIT_NAMES for
+    the 512-lane form or, with large, the 1024-lane form."""
+    buf = np.zeros(len(LIMIT_NAMES), np.uint32)
+    n = int(lib().lancet_settle_emu_limits(1 if large else 0, buf.ctypes.data_as(C.c_void_p), len(buf)))
+    assert n == len(LIMIT_NAMES), n
+    return {k: int(v) for k, v in zip(LIMIT_NAMES, buf)}
 
 
 def run(batch, params=None, settle: bool = True, evt_cap: int = 0, hap_words: int = 0, pre_order: bool = False):
@@ -53,6 +66,8 @@ def run(batch, params=None, settle: bool = True, evt_cap: int = 0, hap_words: in
             buf = np.zeros(max(1, batch.n_windows), np.uint8)
             n = int(L.lancet_settle_emu_flags(C.c_void_p(h), buf.ctypes.data_as(C.c_void_p), len(buf)))
             got["n"], got["flags"] = n, buf
+            why = np.zeros(max(1, batch.n_windows), np.uint32)
+            got["why"] = why if int(L.lancet_settle_emu_why(C.c_void_p(h), why.ctypes.data_as(C.c_void_p), len(why))) >= 0 else None
             free(h)
 
     spy = _Spy()
@@ -89,4 +104,5 @@ def run(batch, params=None, settle: bool = True, evt_cap: int = 0, hap_words: in
     n = got.get("n", -6)
     LAST_SETTLED[:] = [w for w in range(batch.n_windows) if n >= 0 and got["flags"][w]]
     assert n < 0 or n == len(LAST_SETTLED), (n, len(LAST_SETTLED))
+    LAST_WHY[:] = [int(x) for x in got["why"][:batch.n_windows]] if got.get("why") is not None else []
     return v, st, text, haps, list(LAST_SETTLED)
