@@ -329,6 +329,7 @@ int lancet_engine_last_timing(lancet_engine *e, float out[2]);
 #define LANCET_HAP_HEADER_WORDS 8
 #define LANCET_HAP_UNALIGNED 1u   /* flags: compared without alignment (same length, few mismatches: the Hamming short-cut, src/Graph.cc:818-826) */
 #define LANCET_HAP_IS_REF 2u      /* flags: identical to the reference stretch                                                         */
+#define LANCET_HAP_HAS_COVERAGE 4u   /* flags: the entry carries its per-base coverages (lancet_engine_set_haplotype_coverage)          */
 typedef struct lancet_haplotype {
   int32_t  window;            /* index in the batch */
   int32_t  index_in_window;   /* 0, 1, 2 ... in processPath order (across components and k, as -V prints them) */
@@ -337,7 +338,7 @@ typedef struct lancet_haplotype {
   uint32_t len;               /* bases of the path string = the p: line */
   uint32_t word_off;          /* (len + 15) / 16 words of `words` from here */
   int32_t  first_variant, n_variants;   /* seq_in_window of the lancet_variant records this path emitted */
-  uint32_t flags;             /* LANCET_HAP_* ; other bits 0 */
+  uint32_t flags;             /* LANCET_HAP_UNALIGNED | LANCET_HAP_IS_REF | LANCET_HAP_HAS_COVERAGE ; other bits 0 */
 } lancet_haplotype;
 int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window);
 int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **h, uint32_t *n, const uint32_t **words,
@@ -365,6 +366,21 @@ float lancet_engine_haplotype_readback_ms(const lancet_engine *e);
 #define LANCET_HAP_OP_X 8u        /* another base (an N of the reference included)                                        */
 int lancet_engine_set_haplotype_alignments(lancet_engine *e, int on);
 int lancet_engine_results_haplotype_alignments(lancet_engine *e, const uint32_t **cigar_off /* [n + 1] */, const uint32_t **cigar, uint32_t *n_cigar);
+/* ---- ... and how well the reads support every base of it ----
+ * lancet_engine_set_haplotype_coverage(e, 1): the uploads that follow also keep, for every path, the eight coverages the reference prints
+ * per row of its vertical alignment (Graph_t::printVerticalAlignment under -v): for each base of the path the normal and the tumour
+ * coverage, forward and reverse strand (an+ an- at+ at-: fwd / rev of Path_t::covDistr), and for each base of the stretch the reference's
+ * (rn+ rn- rt+ rt-: Ref_t::getNormalCoverage / getTumorCoverage).  The values are the 16-bit counts the kernels hold -- they wrap where the
+ * reference's unsigned short wraps; in lr_mode they are barcode counts, as the reference's are.  Which path base stands beside which
+ * reference base is what the CIGAR says; the coverages themselves do not need the alignments switch.  on is 0 or 1 (else LANCET_E_ARG); the
+ * state rules are those of lancet_engine_set_haplotypes; without the capture itself the switch does nothing.  The words come out of the
+ * window's words_per_window: 2 * (len + ref_len) of them per entry, behind its CIGAR words, and the entry's flags say
+ * LANCET_HAP_HAS_COVERAGE.  A haplotype whose coverages do not fit is one that does not fit: truncated[w] = 1, the ones in front stay whole.
+ * lancet_engine_results_haplotype_coverage: after a run, cov[cov_off[i] .. cov_off[i + 1]) belongs to haplotype i of
+ * lancet_engine_results_haplotypes: 4 * len values an+ an- at+ at- per path base, then 4 * ref_len values rn+ rn- rt+ rt- per base of the
+ * stretch (offset ref_off + j of the window reference).  With the switch off every offset is 0 and n_cov is 0. */
+int lancet_engine_set_haplotype_coverage(lancet_engine *e, int on);
+int lancet_engine_results_haplotype_coverage(lancet_engine *e, const uint32_t **cov_off /* [n + 1] */, const uint16_t **cov, uint32_t *n_cov);
 
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */

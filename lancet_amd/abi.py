@@ -101,6 +101,7 @@ class LancetHaplotype(C.Structure):
 
 HAP_HEADER_WORDS = 8          # LANCET_HAP_HEADER_WORDS: a haplotype of n bases takes this + (n + 15) // 16 words of its window's buffer
 HAP_UNALIGNED, HAP_IS_REF = 1, 2
+HAP_HAS_COVERAGE = 4          # LANCET_HAP_HAS_COVERAGE: the entry carries its per-base coverages (lancet_engine_set_haplotype_coverage)
 HAP_W_NCIGAR = 7              # LANCET_HAP_W_NCIGAR: the header word that counts an entry's CIGAR words (lancet_engine_set_haplotype_alignments)
 HAP_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}      # LANCET_HAP_OP_*: BAM's codes, SAM's extended letters
 
@@ -108,6 +109,14 @@ HAP_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}      # LANCET_HAP_OP_*: BAM's codes, 
 def cigar_to_py(words) -> List[tuple]:
     """CIGAR words (length << 4 | op) as (length, op_char) pairs."""
     return [(int(w) >> 4, HAP_OPS[int(w) & 15]) for w in words]
+
+
+def coverage_to_py(vals: np.ndarray, length: int, ref_len: int) -> dict:
+    """The 4 * (length + ref_len) 16-bit counts of one haplotype as {"path": length x 4 (an+ an- at+ at-), "ref": ref_len x 4 (rn+ rn- rt+ rt-)}."""
+    v = np.asarray(vals, dtype=np.uint16)
+    if v.size != 4 * (length + ref_len):          # (a haplotype of a run without the switch: none)
+        return {"path": np.zeros((0, 4), np.uint16), "ref": np.zeros((0, 4), np.uint16)}
+    return {"path": v[:4 * length].reshape(length, 4).copy(), "ref": v[4 * length:].reshape(ref_len, 4).copy()}
 
 
 def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:

@@ -333,6 +333,7 @@ struct lancet_engine {
   // the windows' length words and buffers, the prefix sums and the dense copy of the read-back, the last run's result and what its read-back took
   uint32_t hap_words = 0;
   uint32_t hap_aln = 0;       // lancet_engine_set_haplotype_alignments: the next upload's entries carry their CIGAR words (EngineCaps::hap_aln)
+  uint32_t hap_cov = 0;       // lancet_engine_set_haplotype_coverage: ... and their per-base coverages (EngineCaps::hap_cov)
   DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
   LcHapResult hap;
   float ms_hap = 0;
@@ -552,6 +553,16 @@ int lancet_engine_set_haplotype_alignments(lancet_engine *e, int on) {
   return LANCET_OK;
 }
 
+// ... and the read support of every base of path and stretch.  Same rules again.
+int lancet_engine_set_haplotype_coverage(lancet_engine *e, int on) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotype_coverage while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotype_coverage between an upload and its run"; return LANCET_E_STATE; }
+  if (on != 0 && on != 1) { e->err = "set_haplotype_coverage: on is 0 or 1"; return LANCET_E_ARG; }
+  e->hap_cov = (uint32_t)on;
+  return LANCET_OK;
+}
+
 static int up(lancet_engine *e, DevBuf &b, const void *src, size_t bytes) {
   if (b.ensure(bytes ? bytes : 1)) { e->err = "hipMalloc failed"; return LANCET_E_OOM; }
   if (bytes) HIPCHK(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
@@ -627,6 +638,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   e->caps.evt_level = e->caps2.evt_level = e->evt_cap ? e->evt_level : 0u;      // (the engine's own setting, whatever the helper read from the environment)
   e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
   e->caps.hap_aln = e->caps2.hap_aln = e->hap_words ? e->hap_aln : 0u;
+  e->caps.hap_cov = e->caps2.hap_cov = e->hap_words ? e->hap_cov : 0u;
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
   e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
@@ -1264,7 +1276,7 @@ int lancet_engine_submit(lancet_engine *e) {
   e->ran = false;
   e->variants.clear(); e->blob.clear(); e->stats.clear(); e->evt_len.clear(); e->evt.clear(); e->variants_lr.clear(); e->bx_blob.clear();
   e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
-  e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear();
+  e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear(); e->hap.cov_off.assign(1, 0u); e->hap.cov.clear();
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1513,6 +1525,15 @@ int lancet_engine_results_haplotype_alignments(lancet_engine *e, const uint32_t 
   if (cigar_off) *cigar_off = e->hap.cigar_off.data();
   if (cigar) *cigar = e->hap.cigar.data();
   if (n_cigar) *n_cigar = (uint32_t)e->hap.cigar.size();
+  return LANCET_OK;
+}
+int lancet_engine_results_haplotype_coverage(lancet_engine *e, const uint32_t **cov_off, const uint16_t **cov, uint32_t *n_cov) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  if (e->hap.cov_off.size() != e->hap.h.size() + 1) e->hap.cov_off.assign(e->hap.h.size() + 1, (uint32_t)e->hap.cov.size());
+  if (cov_off) *cov_off = e->hap.cov_off.data();
+  if (cov) *cov = e->hap.cov.data();
+  if (n_cov) *n_cov = (uint32_t)e->hap.cov.size();
   return LANCET_OK;
 }
 // milliseconds the last run's read-back of the haplotypes took on the host clock (lengths, compaction, copy, parsing); 0 with the capture off

@@ -5469,6 +5469,46 @@ DEVNI void hap_cigar(Ctx &c, int m, int hd, int L) {
   WG_FOR(r, nr) { const uint32_t s = pos[r]; q[r] = ((pos[r + 1] - s) << 4) | hap_col_op(ra[s], pa[s]); }
   WG_SYNC();
 }
+// ... and how well the reads support it (EngineCaps::hap_cov), behind the CIGAR words: the eight coverages of a row of
+// printVerticalAlignment (reference src/Graph.cc:749-783) for every base of the path and of the stretch, whichever columns the alignment
+// pairs them in.  2 * m words for the path -- base P: an+ | an- << 16, at+ | at- << 16, the fwd / rev of coverageN[P] / coverageT[P]
+// (path_cov_at's first two per sample) -- then 2 * seq_len words for the stretch -- base j: rn+ | rn- << 16, rt+ | rt- << 16,
+// getNormalCoverage()[j] / getTumorCoverage()[j] (src/Ref.hh:134-135): computeCoverage's vector from Ref_t::trim5 on, the index
+// ref_cov_at's callers use (S.trim5 is S.seq_t5 & 0xFFFF, the reference's unsigned short: the entry's HP_W_REFOFF, S.seq_t5, and this index agree
+// for every window reference below 64k bases, and max_w is far below that).  Every lane of the workgroup takes a base per trip (XG_FOR: the helper waves of the fat form too) and stores
+// its two words as one 8-byte word where the entry's position in the buffer allows, so that a wave writes contiguous memory.  Once per
+// path, before anything walks it, like hap_cigar; words that do not fit mark the window HP_TRUNC.  The entry says LANCET_HAP_HAS_COVERAGE.
+DEVNI void hap_cov(Ctx &c, int m) {
+  LC_WS &S = LC_SREF(c); LC_GLOBAL Work &W = *LC_CTX(c).W;
+  const uint32_t cap = LC_CTX(c).C->hap_cap;
+  const int w = wg_uniform(S.w);
+  const int n = wg_uniform(S.seq_len), t5 = wg_uniform(S.trim5), reflen = wg_uniform(S.reflen);
+  LC_GLOBAL uint32_t *lenp = LC_HAP_LEN(c) + w;
+  WG_SYNC();                                                               // (hap_cigar's mark and its word count have landed)
+  const uint32_t cur = (uint32_t)wg_uniform((int)ld2(lenp));
+  if (cur & HP_TRUNC) return;
+  LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)w * cap + cur;
+  const uint32_t used = cur + HP_HDR + ((uint32_t)m + 15u) / 16u + (uint32_t)wg_uniform((int)ld2(p + HP_W_NCIG));
+  WG_SYNC();                                                               // (every wave has read the words before lane 0 may mark them)
+  const uint32_t need = 2u * ((uint32_t)m + (uint32_t)n);
+  if (used > cap || need > cap - used) { WG_LANE0 { st2(lenp, cur | HP_TRUNC); } return; }
+  LC_GLOBAL uint32_t *q = LC_HAP_OUT(c) + (size_t)w * cap + used;
+  LC_GLOBAL uint32_t *qr = q + 2u * (uint32_t)m;
+  const bool wide = (((unsigned long long)(uintptr_t)q) & 7ull) == 0;     // (2 * m words further on the stretch's words lie the same way)
+  XG_FOR(P, m) {
+    const uint16_t *kc = W.gr[SD_KMER(W.pdesc[P])].kc;                     // Tf Tr Nf Nr (desc_cov)
+    const uint32_t an = (uint32_t)kc[2] | ((uint32_t)kc[3] << 16), at = (uint32_t)kc[0] | ((uint32_t)kc[1] << 16);
+    if (wide) *(LC_GLOBAL unsigned long long *)(q + 2 * P) = (unsigned long long)an | ((unsigned long long)at << 32);
+    else { q[2 * P] = an; q[2 * P + 1] = at; }
+  }
+  XG_FOR(j, n) {
+    uint32_t rn = 0, rt = 0;
+    if (t5 + j < reflen) { const uint16_t *r = W.refcov + 4 * (t5 + j); rt = (uint32_t)r[0] | ((uint32_t)r[1] << 16); rn = (uint32_t)r[2] | ((uint32_t)r[3] << 16); }
+    if (wide) *(LC_GLOBAL unsigned long long *)(qr + 2 * j) = (unsigned long long)rn | ((unsigned long long)rt << 32);
+    else { qr[2 * j] = rn; qr[2 * j + 1] = rt; }
+  }
+  WG_LANE0 { p[HP_W_FLAGS] |= LANCET_HAP_HAS_COVERAGE; }
+}
 // lane 0, after the path's walk: the records it emitted, and the entry counts
 DEV void hap_close(Ctx &c) {
   LC_WS &S = LC_SREF(c);
@@ -5478,7 +5518,8 @@ DEV void hap_close(Ctx &c) {
   if (cur & HP_TRUNC) return;
   LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)S.w * cap + cur;
   p[HP_W_NVAR] = (uint32_t)S.emit_seq - p[HP_W_FIRST];
-  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG]);
+  const uint32_t ncov = (p[HP_W_FLAGS] & LANCET_HAP_HAS_COVERAGE) ? 2u * (p[HP_W_LEN] + p[HP_W_REFLEN]) : 0u;      // (hap_cov's words, behind the CIGAR's)
+  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG] + ncov);
 }
 
 // eka (reference src/Graph.cc:1430-1501) via countRefPath (:2420-2445)
@@ -5487,6 +5528,7 @@ DEVNI void count_ref_path(Ctx &c) {
   if (wg_bcastu(&S.source) == LC_NIL) return;
   const bool hap_on = wg_uniform((int)LC_CTX(c).C->hap_cap) != 0;      // (haplotype capture: the one test of a run without it)
   const bool hap_aln = hap_on && wg_uniform((int)LC_CTX(c).C->hap_aln) != 0;      // (... with the CIGARs: read with the capture on only)
+  const bool hap_cvg = hap_on && wg_uniform((int)LC_CTX(c).C->hap_cov) != 0;      // (... with the per-base coverages: likewise)
   if (wg_bcastu(&S.sink) != LC_NIL) {
     WG_LANE0 { evt(c, EV_SEARCH, (uint32_t)W.gr[S.source].comp); S.tmp0 = S.tmp1 = S.tmp2 = 0; S.part[0] = 0; S.part[1] = 0; S.part[2] = 0; S.part[3] = 0; S.pc_i = 0; S.pc_rd = 0; }
     const bool replay = wg_bcast(&S.pc_ok) != 0;             // the paths are the ones findRepeatsInGraphPaths found (pcache_store)
@@ -5568,6 +5610,8 @@ DEVNI void count_ref_path(Ctx &c) {
       }
       // ... and its CIGAR, now that the alignment is known: before the walk, so that a path the wave driver hands to the one-lane driver has one
       if (hap_aln && !wg_bcast(&S.overflow)) hap_cigar(c, (int)wg_bcastu(&S.part[5]), hd, (int)wg_bcastu(&S.part[7]));
+      // ... and its coverages behind that: pdesc and refcov are what the walk is about to read, whether the path is new or replayed, differs or not
+      if (hap_cvg && !wg_bcast(&S.overflow)) hap_cov(c, (int)wg_bcastu(&S.part[5]));
       PHASE(c, 14);
       if (hd == 0 && !old_walk) {
         SUBPHASE(c, 4, 7);

@@ -33,6 +33,12 @@
 // path=.., FLAG 0, POS = first base of the stretch, MAPQ 255, the CIGAR in = X I D (a D run at either end is dropped, POS moves past a leading
 // one), SEQ, and the tags kk:i (k) cp:i (component) pi:i (index in window) wn:Z (window) vf:i / vn:i (first_variant, n_variants) fl:i (flags).
 // Alone or with --haplotypes; the same rules (not with --ranks above 1, left out of ##cmdline); the buffer is 64 words per path larger.
+// --haplotype-coverage FILE: per haplotype, in the same order, the --haplotypes header line up to ref=off+len and below it the table the
+// reference prints for that path under -v (Graph_t::printVerticalAlignment, src/Graph.cc:749-783), byte for byte: the `Pos r p d an+ ...` line
+// and one row per alignment column with the path's and the reference's normal / tumour coverage per strand
+// (lancet_engine_set_haplotype_coverage; the alignments are turned on with it, the table needs the columns).  Alone or with the other two;
+// the same rules; the buffer is 2 * (2 * longest + --max-indel-len + 256) words per path larger.  With --haplotype-sam every SAM record
+// gains the tags nf nr tf tr (B:S): the path's an+ an- at+ at-, one value per SEQ base.
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
 
@@ -65,7 +71,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -81,6 +87,8 @@ uint32_t hap_words_for(uint32_t longest, int max_indel_len) {
 }
 // --haplotype-sam: 64 more words per path for the runs of its CIGAR
 uint32_t hap_cigar_words() { return MV_PATHS * 64u; }
+// --haplotype-coverage: two words per base of every path and of its stretch (four 16-bit counts each)
+uint32_t hap_cov_words(uint32_t longest, int max_indel_len) { return MV_PATHS * 2u * (2u * longest + (uint32_t)max_indel_len + 256u); }
 // --haplotype-sam: (name, length) of the contigs of a FASTA file in its order -- from its .fai when there is one, else from the file itself
 bool fasta_contigs(const std::string &path, std::vector<std::pair<std::string, long>> *out) {
   out->clear();
@@ -137,6 +145,8 @@ void usage() {
         "                                       at full throughput; same VCF, the option is left out of ##cmdline; not with --ranks above 1\n"
         "   --haplotype-sam <file>            : the same haplotypes as SAM records on the contig, CIGAR in = X I D as the window kernel aligned them;\n"
         "                                       alone or with --haplotypes, same rules\n"
+        "   --haplotype-coverage <file>       : per haplotype its header line and the reference's -v table of per-base coverages (Pos r p d an+ an- at+ at-\n"
+        "                                       rn+ rn- rt+ rt-); alone or with the other two, same rules; adds the tags nf nr tf tr to --haplotype-sam\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -151,7 +161,7 @@ int main(int argc, char **argv) {
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
-  std::string rendezvous, hap_file, sam_file;
+  std::string rendezvous, hap_file, sam_file, cov_file;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -181,7 +191,7 @@ int main(int argc, char **argv) {
     else if (L == "min-report-unit") min_report_unit = atoi(v); else if (L == "min-report-len") min_report_len = atoi(v); else if (L == "dist-from-str") dist_from_str = atoi(v);
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
-    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v;
+    else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v; else if (L == "haplotype-coverage") cov_file = v;
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -190,6 +200,7 @@ int main(int argc, char **argv) {
   if (ranks < 0 || (ranks == 0 && rank >= 0) || (ranks > 0 && rank >= ranks)) return die("--ranks must be >= 1 and --rank one of 0 .. ranks-1");
   if (!hap_file.empty() && ranks > 1) return die("--haplotypes is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (!sam_file.empty() && ranks > 1) return die("--haplotype-sam is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (!cov_file.empty() && ranks > 1) return die("--haplotype-coverage is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -304,11 +315,14 @@ int main(int argc, char **argv) {
     for (const auto &ct : contigs) fprintf(sam_out, "@SQ\tSN:%s\tLN:%ld\n", ct.first.c_str(), ct.second);
     fputs("@PG\tID:lancet_gpu\tPN:lancet_gpu\n", sam_out);
   }
-  const bool sam_on = sam_out != nullptr;
-  const bool hap_on = hap_out != nullptr || sam_on;      // either file turns the capture on; the SAM one the alignments as well
-  const uint32_t hap_extra = sam_on ? hap_cigar_words() : 0u;
+  FILE *cov_out = nullptr;
+  if (!cov_file.empty() && !(cov_out = fopen(cov_file.c_str(), "w"))) return die("cannot write " + cov_file);
+  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr;
+  const bool aln_on = sam_on || cov_on;                  // the table is laid out by the alignment's columns
+  const bool hap_on = hap_out != nullptr || aln_on;      // any of the files turns the capture on; the SAM and the coverage one the alignments as well
+  auto hap_extra_for = [&](uint32_t longest) -> uint32_t { return (aln_on ? hap_cigar_words() : 0u) + (cov_on ? hap_cov_words(longest, max_indel_len) : 0u); };
   long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
-  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
@@ -362,7 +376,9 @@ int main(int argc, char **argv) {
       const lancet_haplotype *hp; uint32_t nh = 0, nwords = 0; const uint32_t *words; const uint8_t *trunc;
       if (lancet_engine_results_haplotypes(sl.e, &hp, &nh, &words, &nwords, &trunc) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       const uint32_t *cig_off = nullptr, *cig = nullptr; uint32_t ncig = 0;
-      if (sam_on && lancet_engine_results_haplotype_alignments(sl.e, &cig_off, &cig, &ncig) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+      if (aln_on && lancet_engine_results_haplotype_alignments(sl.e, &cig_off, &cig, &ncig) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+      const uint32_t *cov_off = nullptr; const uint16_t *cov = nullptr; uint32_t ncov = 0;
+      if (cov_on && lancet_engine_results_haplotype_coverage(sl.e, &cov_off, &cov, &ncov) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
       for (uint32_t i = 0; i < nh; ++i) {
         const lancet_haplotype &x = hp[i];
@@ -372,6 +388,9 @@ int main(int argc, char **argv) {
         char head[256];
         std::string seq((size_t)x.len, 'A');
         for (uint32_t b = 0; b < x.len; ++b) seq[b] = "ACGT"[(words[x.word_off + b / 16u] >> (2u * (b % 16u))) & 3u];
+        // the haplotype's coverages: 4 per path base (an+ an- at+ at-), then 4 per base of the stretch (rn+ rn- rt+ rt-)
+        const uint16_t *pcv = nullptr, *rcv = nullptr;
+        if (cov_on && cov_off[i + 1] <= ncov && cov_off[i + 1] - cov_off[i] == 4u * (x.len + x.ref_len)) { pcv = cov + cov_off[i]; rcv = pcv + 4u * (size_t)x.len; }
         if (hap_out) {
           snprintf(head, sizeof head, ">%s|k=%u|comp=%u|path=%d|ref=%u+%u|variants=%d+%d\n", hdr, (unsigned)x.kmer, (unsigned)x.component,
                    x.index_in_window, x.ref_off, x.ref_len, x.first_variant, x.n_variants);
@@ -395,9 +414,39 @@ int main(int argc, char **argv) {
             j.hapsam += op == LANCET_HAP_OP_EQ ? '=' : op == LANCET_HAP_OP_X ? 'X' : op == LANCET_HAP_OP_I ? 'I' : 'D';
           }
           j.hapsam += "\t*\t0\t0\t"; j.hapsam += seq;
-          snprintf(head, sizeof head, "\t*\tkk:i:%u\tcp:i:%u\tpi:i:%d\twn:Z:%s\tvf:i:%d\tvn:i:%d\tfl:i:%u\n", (unsigned)x.kmer, (unsigned)x.component, x.index_in_window, hdr,
+          snprintf(head, sizeof head, "\t*\tkk:i:%u\tcp:i:%u\tpi:i:%d\twn:Z:%s\tvf:i:%d\tvn:i:%d\tfl:i:%u", (unsigned)x.kmer, (unsigned)x.component, x.index_in_window, hdr,
                    x.first_variant, x.n_variants, x.flags);
           j.hapsam += head;
+          if (pcv) for (int q = 0; q < 4; ++q) {          // --haplotype-coverage as well: the path's an+ an- at+ at-, one value per SEQ base
+            j.hapsam += q == 0 ? "\tnf:B:S" : q == 1 ? "\tnr:B:S" : q == 2 ? "\ttf:B:S" : "\ttr:B:S";
+            for (uint32_t b = 0; b < x.len; ++b) { j.hapsam += ','; j.hapsam += std::to_string((unsigned)pcv[4u * b + (uint32_t)q]); }
+          }
+          j.hapsam += '\n';
+        }
+        if (cov_on) {
+          // the reference's table (printVerticalAlignment): Pos is the path index and stays on a deletion column; the side with a gap has empty cells
+          const uint32_t c0 = cig_off[i], c1 = cig_off[i + 1];
+          const std::string *raw = (size_t)x.window < sl.raw.size() ? &sl.raw[(size_t)x.window] : nullptr;
+          const bool ok = pcv && c1 <= ncig && c0 <= c1 && raw && (uint64_t)x.ref_off + x.ref_len <= raw->size();      // (else: no table, the haplotype still counts)
+          snprintf(head, sizeof head, ">%s|k=%u|comp=%u|path=%d|ref=%u+%u\n", hdr, (unsigned)x.kmer, (unsigned)x.component, x.index_in_window, x.ref_off, x.ref_len);
+          std::string &o = j.hapcov;
+          if (ok) { o += head; o += "Pos\tr\tp\td\tan+\tan-\tat+\tat-\trn+\trn-\trt+\trt-\n"; }
+          uint32_t pk = 0, rj = 0;
+          auto four = [&](const uint16_t *v) { for (int q = 0; q < 4; ++q) { o += '\t'; if (v) o += std::to_string((unsigned)v[q]); } };
+          for (uint32_t q = c0; ok && q < c1; ++q) {
+            const uint32_t op = cig[q] & 15u;
+            const bool ins = op == LANCET_HAP_OP_I, del = op == LANCET_HAP_OP_D;
+            for (uint32_t n = cig[q] >> 4; n > 0 && (del || pk < x.len) && (ins || rj < x.ref_len); --n) {
+              o += std::to_string(pk); o += '\t';
+              o += ins ? '-' : (char)toupper((unsigned char)(*raw)[x.ref_off + rj]); o += '\t';
+              o += del ? '-' : seq[pk]; o += '\t';
+              o += ins ? '^' : del ? 'v' : op == LANCET_HAP_OP_EQ ? ' ' : 'x';
+              four(del ? nullptr : pcv + 4u * pk); four(ins ? nullptr : rcv + 4u * rj);
+              o += '\n';
+              if (!del) ++pk;
+              if (!ins) ++rj;
+            }
+          }
         }
         ++n_hap;
       }
@@ -412,6 +461,7 @@ int main(int argc, char **argv) {
       if (!j.trace.empty()) fputs(j.trace.c_str(), stderr);
       if (!j.hapfa.empty() && fwrite(j.hapfa.data(), 1, j.hapfa.size(), hap_out) != j.hapfa.size()) { fail = "cannot write " + hap_file; return false; }
       if (!j.hapsam.empty() && fwrite(j.hapsam.data(), 1, j.hapsam.size(), sam_out) != j.hapsam.size()) { fail = "cannot write " + sam_file; return false; }
+      if (!j.hapcov.empty() && fwrite(j.hapcov.data(), 1, j.hapcov.size(), cov_out) != j.hapcov.size()) { fail = "cannot write " + cov_file; return false; }
       int arc = LANCET_OK;
       if (ranked) {                                  // the records travel: keyed, reduced, window numbers of the whole tiling
         if (!j.v.empty()) {
@@ -483,12 +533,13 @@ int main(int argc, char **argv) {
           uint32_t longest = 0;
           for (int32_t i = 0; i < SL.n_windows; ++i) longest = std::max(longest, SL.ref_off[i + 1] - SL.ref_off[i]);
           if (more_verbose && lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
-          if (hap_on && (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, sam_on ? 1 : 0) != LANCET_OK))
+          if (hap_on && (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
+                         lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK))
             return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
         }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
         t_engine += now() - t0; t0 = now();
-        if (rc == LANCET_OK && more_verbose) {
+        if (rc == LANCET_OK && (more_verbose || cov_on)) {      // (--haplotype-coverage prints the stretch's bases)
           sl.raw.assign((size_t)nk, std::string());
           for (int32_t w = 0, i = 0; w < nk; ++w) {
             while (i < SL.n_windows && SL.widx[i] != sl.kept[(size_t)w]) ++i;
@@ -515,7 +566,9 @@ int main(int argc, char **argv) {
     if (!taken && hap_on) {
       uint32_t longest = 0;
       for (int32_t w = 0; w < nk; ++w) longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]);
-      if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, sam_on ? 1 : 0) != LANCET_OK)
+      if (cov_on && !more_verbose) { sl.raw.assign((size_t)nk, std::string()); for (int32_t w = 0; w < nk; ++w) sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
+      if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
+          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK)
         return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
@@ -555,8 +608,12 @@ int main(int argc, char **argv) {
       if (fclose(sam_out) != 0) return die("cannot write " + sam_file);
       fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, sam_file.c_str());
     }
+    if (cov_on) {
+      if (fclose(cov_out) != 0) return die("cannot write " + cov_file);
+      fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, cov_file.c_str());
+    }
     if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
-                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_file.c_str());
+                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_file.c_str());
   }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
@@ -603,7 +660,7 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
-    if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0) { ++i; continue; }  // (a second output of the same run)
+    if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0 || strcmp(argv[i], "--haplotype-coverage") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

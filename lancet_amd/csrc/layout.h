@@ -132,6 +132,8 @@ struct EngineCaps {
                             re-run tier max(table_cap, occ_cap) -- an occurrence is flagged at most once, so that list cannot fill up */
   uint32_t hap_cap;      /* haplotype capture: words of the window's buffer (DevOut::hap_out), 0 = off (lancet_engine_set_haplotypes) */
   uint32_t hap_aln;      /* ... with every entry's CIGAR words behind its path words (lancet_engine_set_haplotype_alignments); read only where hap_cap != 0 */
+  uint32_t hap_cov;      /* ... with every base's read support behind the CIGAR words: 2 * (len + ref_len) words, the entry flagged LANCET_HAP_HAS_COVERAGE
+                            (lancet_engine_set_haplotype_coverage; kernels.h hap_cov); read only where hap_cap != 0 */
   uint32_t settle;       /* the build kernel may settle reference-only windows (PreHdr::settled): set by the engine when nothing is on that wants to
                             see such a window's graph -- trace, haplotype capture, linked reads -- and LANCET_NO_SETTLE is not set.  1: the reference chain beside components without a source
                              ; 2: the chain has to be the whole graph (LANCET_SETTLE_CHAIN_ONLY=1) */
@@ -142,6 +144,9 @@ struct EngineCaps {
  * An entry is HP_HDR header words and the path string behind them, 16 bases to a word (2 bits per base, first base in the low bits);
  * with EngineCaps::hap_aln the path's alignment to the reference stretch follows, header word HP_W_NCIG words of length << 4 | op, one per
  * maximal run of columns of one class (HP_OP_*: BAM's codes; kernels.h hap_cigar).  Without it that word is 0 and nothing follows.
+ * With EngineCaps::hap_cov the coverages follow behind those, and LANCET_HAP_HAS_COVERAGE in HP_W_FLAGS says so: two words per path base
+ * (an+ | an- << 16, at+ | at- << 16), HP_W_LEN of them, then two per base of the stretch (rn+ | rn- << 16, rt+ | rt- << 16), HP_W_REFLEN of
+ * them -- the 16-bit counts the kernels hold, the cells of a row of the reference's vertical alignment (kernels.h hap_cov).
  * DevOut::hap_len[w] holds the words of the window's CLOSED entries: the entry of the path being walked lies behind them and counts
  * once its walk is through (kernels.h hap_open / hap_close).  HP_TRUNC in that word: an entry did not fit, nothing is written after it. */
 #define HP_HDR 8u
@@ -418,8 +423,8 @@ struct DevOut {
 /* Host emulation of the kernels only: where the haplotype capture writes and how large a window's buffer is.  The emulator's driver
  * fills a DevOut of its own; a test build that wants the capture sets this before the run (tests/hap_emu), lc_caps_for_sizes and the
  * kernels read it in place of DevOut::hap_len / hap_out. */
-struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; uint32_t aln; /* EngineCaps::hap_aln of the run */ };
-inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr, 0u};
+struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; uint32_t aln; /* EngineCaps::hap_aln of the run */ uint32_t cov; /* ... and its hap_cov */ };
+inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr, 0u, 0u};
 #define LC_HAP_LEN(c) (lc_emu_hap_sink.len)
 #define LC_HAP_OUT(c) (lc_emu_hap_sink.out)
 #else

@@ -1,6 +1,8 @@
-"""python tools/haplotype_cost.py [windows] [--alignments] -- cost of the haplotype capture on the bench batch (workload.make_scan_batch(32768, 30, 30, seed=22), the batch resident): wall time of
+"""python tools/haplotype_cost.py [windows] [--alignments] [--coverage] -- cost of the haplotype capture on the bench batch (workload.make_scan_batch(32768, 30, 30, seed=22), the batch resident): wall time of
 lancet_engine_run per step with the capture off and on (lancet_gpu's size for the batch), the kernels' time, and the read-back.
---alignments: also with every haplotype's CIGAR (lancet_engine_set_haplotype_alignments; lancet_gpu --haplotype-sam's size for the batch), and the CIGAR words per batch."""
+--alignments: also with every haplotype's CIGAR (lancet_engine_set_haplotype_alignments; lancet_gpu --haplotype-sam's size for the batch), and the CIGAR words per batch.
+--coverage: also with every base's coverages on top of the CIGARs (lancet_engine_set_haplotype_coverage; lancet_gpu --haplotype-coverage's size for the batch): the window kernel's own time,
+the read-back, the words per window that are used, the truncated windows; every haplotype's arrays are checked for their shape."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,33 +10,49 @@ import numpy as np
 from lancet_amd import abi, engine, workload
 import hap_cases as hc
 
-args = [a for a in sys.argv[1:] if a != "--alignments"]
+args = [a for a in sys.argv[1:] if a not in ("--alignments", "--coverage")]
 aln = "--alignments" in sys.argv[1:]
+cov = "--coverage" in sys.argv[1:]
 n = int(args[0]) if args else 32768
 t = time.time(); batch = workload.make_scan_batch(n, 30.0, 30.0, seed=22); print("batch s", round(time.time() - t, 1), flush=True)
 p = abi.default_params(min_k=11, max_k=101)
 words = hc.ample_words(batch, p)
+longest = max(int(batch.ref_off[w + 1] - batch.ref_off[w]) for w in range(batch.n_windows))
+cov_words = words + 32 * 64 + 32 * 2 * (2 * longest + int(p.max_indel_len) + 256)
 res = {}
-runs = [("off", 0, False), ("on", words, False)] + ([("aln", words + 32 * 64, True)] if aln else []) + [("off2", 0, False), ("on2", words, False)] + ([("aln2", words + 32 * 64, True)] if aln else [])
-for label, hw, al in runs:
-    eng = engine.Engine(p, haplotype_words=hw, haplotype_alignments=al)
+once = [("off", 0, False, False), ("on", words, False, False)] + ([("aln", words + 32 * 64, True, False)] if aln or cov else []) + ([("cov", cov_words, True, True)] if cov else [])
+runs = once + [(l + "2", hw, al, cv) for l, hw, al, cv in once]
+for label, hw, al, cv in runs:
+    eng = engine.Engine(p, haplotype_words=hw, haplotype_alignments=al, haplotype_coverage=cv)
     eng.upload(batch)
-    wall, kern, rb = [], [], []
+    names = eng.kernel_names()
+    wi = names.index("window_kernel") if "window_kernel" in names else None
+    wall, kern, rb, wk = [], [], [], []
     for it in range(12):
         t = time.perf_counter(); eng.run(); wall.append(1000 * (time.perf_counter() - t))
         kern.append(eng.timing_ms()[0]); rb.append(eng.haplotype_readback_ms())
+        wk.append(eng.kernel_times()[wi] if wi is not None else eng.timing_ms()[1])
     v, st = eng.results()
     haps, trunc = ([], []) if not hw else eng.haplotypes()
     res[label] = (v, st)
     med = lambda a: float(np.median(a[2:]))
-    print(f"{label}: words/window {hw} wall ms/step median {med(wall):.2f} (min {min(wall[2:]):.2f} max {max(wall[2:]):.2f}) kernels ms {med(kern):.2f} read-back ms {med(rb):.2f} "
-          f"haplotypes {len(haps)} bases {sum(h['len'] for h in haps)} cigar words {sum(len(h.get('cigar', ())) for h in haps)} truncated windows {sum(trunc)} records {len(v)} "
+    used = sum(hc.words_of(h) + len(h.get("cigar", ())) + (2 * (h["len"] + h["ref_len"]) if "cov" in h else 0) for h in haps)
+    print(f"{label}: words/window {hw} wall ms/step median {med(wall):.2f} (min {min(wall[2:]):.2f} max {max(wall[2:]):.2f}) kernels ms {med(kern):.2f} window kernel ms {med(wk):.2f} "
+          f"read-back ms {med(rb):.2f} haplotypes {len(haps)} bases {sum(h['len'] for h in haps)} cigar words {sum(len(h.get('cigar', ())) for h in haps)} "
+          f"used words/window {used / max(1, batch.n_windows):.1f} truncated windows {sum(trunc)} records {len(v)} "
           f"bad {sum(1 for s in st if s['status'] < 0)} rerun {eng.rerun_count()}", flush=True)
-    if hw and label in ("on", "aln"):
-        hc.check_shape(batch, st, haps, trunc); hc.check_link(batch, v, st, haps, windows=[w for w in range(batch.n_windows) if not trunc[w]])
-        print("link check ok on", batch.n_windows, "windows", flush=True)
-    if label == "aln":
+    if cv:
+        import hap_cov_cases as hcc
+        haps_plain = hcc.strip_cov(haps)
+        if label == "cov":
+            hcc.check_shape(haps)
+            print("coverage shape ok on", len(haps), "haplotypes;", sum(1 for h in haps if (h["cov"]["path"][:, 0] != h["cov"]["path"][:, 1]).any()), "with an+ != an- somewhere", flush=True)
+        haps = haps_plain
+    if hw and label in ("on", "aln", "cov"):
         import hap_align_cases as hac
+        hc.check_shape(batch, st, hac.strip_cigar(haps), trunc); hc.check_link(batch, v, st, haps, windows=[w for w in range(batch.n_windows) if not trunc[w]])
+        print("link check ok on", batch.n_windows, "windows", flush=True)
+    if label in ("aln", "cov"):
         hac.check_cigars(batch, haps, v)
         print("cigar check ok on", len(haps), "haplotypes", flush=True)
     eng.close()
