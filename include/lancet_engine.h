@@ -330,6 +330,7 @@ int lancet_engine_last_timing(lancet_engine *e, float out[2]);
 #define LANCET_HAP_UNALIGNED 1u   /* flags: compared without alignment (same length, few mismatches: the Hamming short-cut, src/Graph.cc:818-826) */
 #define LANCET_HAP_IS_REF 2u      /* flags: identical to the reference stretch                                                         */
 #define LANCET_HAP_HAS_COVERAGE 4u   /* flags: the entry carries its per-base coverages (lancet_engine_set_haplotype_coverage)          */
+#define LANCET_HAP_HAS_SUPPORT 8u    /* flags: the entry carries the counts of the reads that fit it (lancet_engine_set_haplotype_support) */
 typedef struct lancet_haplotype {
   int32_t  window;            /* index in the batch */
   int32_t  index_in_window;   /* 0, 1, 2 ... in processPath order (across components and k, as -V prints them) */
@@ -338,7 +339,7 @@ typedef struct lancet_haplotype {
   uint32_t len;               /* bases of the path string = the p: line */
   uint32_t word_off;          /* (len + 15) / 16 words of `words` from here */
   int32_t  first_variant, n_variants;   /* seq_in_window of the lancet_variant records this path emitted */
-  uint32_t flags;             /* LANCET_HAP_UNALIGNED | LANCET_HAP_IS_REF | LANCET_HAP_HAS_COVERAGE ; other bits 0 */
+  uint32_t flags;             /* LANCET_HAP_UNALIGNED | LANCET_HAP_IS_REF | LANCET_HAP_HAS_COVERAGE | LANCET_HAP_HAS_SUPPORT ; other bits 0 */
 } lancet_haplotype;
 int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window);
 int lancet_engine_results_haplotypes(lancet_engine *e, const lancet_haplotype **h, uint32_t *n, const uint32_t **words,
@@ -381,6 +382,30 @@ int lancet_engine_results_haplotype_alignments(lancet_engine *e, const uint32_t 
  * stretch (offset ref_off + j of the window reference).  With the switch off every offset is 0 and n_cov is 0. */
 int lancet_engine_set_haplotype_coverage(lancet_engine *e, int on);
 int lancet_engine_results_haplotype_coverage(lancet_engine *e, const uint32_t **cov_off /* [n + 1] */, const uint16_t **cov, uint32_t *n_cov);
+/* ---- ... and how many reads carry it rather than its rivals ----
+ * lancet_engine_set_haplotype_support(e, 1, max_mismatches): after the windows of the runs that follow are through, a kernel of its own
+ * compares every read of a window with every haplotype of it (XOR and popcount over the packed words, both still resident) and counts,
+ * per haplotype and read class Tf Tr Nf Nr (tumour / normal, forward / reverse: the order of the coverages' counters), the reads that fit.
+ * All of it is integer arithmetic, and this is its definition -- the reference has no such value:
+ *   A read is taken as the kernels see it: trimmed (Graph_t::trim), t bases, in BAM orientation, as the path strings are.  The GROUP of a
+ *   haplotype is its (kmer, component): haplotypes of one group share their stretch and compete, others do not.
+ *   A placement of a read on a haplotype of M bases at k is an offset o, negative ones included, whose overlap
+ *   v(o) = min(t, M - o) - max(0, -o) is at least k: the read may hang over either end of the path.  mm(o) counts the overlap positions i
+ *   with read[i] != path[o + i]; d = min over o of mm(o).  A read with t < k has no d for that haplotype.
+ *   The read FITS haplotype h iff d(h) is the smallest d over the haplotypes of h's group and d(h) <= max_mismatches; it fits h ALONE iff
+ *   it fits no other haplotype of the group.
+ * Limits: base qualities are not looked at; placements are ungapped; rivals are the haplotypes of the same (k, component) only; in a
+ * truncated window the counts are those among its whole entries.
+ * on is 0 or 1, max_mismatches 0..255 (else LANCET_E_ARG); the state rules are those of lancet_engine_set_haplotypes; without the
+ * capture itself the switch does nothing.  The words come out of the window's words_per_window: 8 per entry, behind its coverage words,
+ * and the entry's flags say LANCET_HAP_HAS_SUPPORT; a haplotype whose 8 words do not fit is one that does not fit.
+ * lancet_engine_results_haplotype_support: after a run, support[8 * i .. 8 * i + 8) belongs to haplotype i of
+ * lancet_engine_results_haplotypes: fit Tf Tr Nf Nr, then alone Tf Tr Nf Nr.  NULL with the switch off (or no haplotype).
+ * lancet_engine_haplotype_support_ms: HIP-event milliseconds of the support kernel in the last run; 0 with the switch off.  (The kernel is
+ * not one of lancet_engine_kernel_name's: it runs in lancet_engine_wait, behind the re-run tier.) */
+int lancet_engine_set_haplotype_support(lancet_engine *e, int on, int max_mismatches);
+int lancet_engine_results_haplotype_support(lancet_engine *e, const uint32_t **support /* [n][8]: fit Tf Tr Nf Nr, alone Tf Tr Nf Nr */);
+float lancet_engine_haplotype_support_ms(const lancet_engine *e);
 
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */

@@ -102,6 +102,7 @@ class LancetHaplotype(C.Structure):
 HAP_HEADER_WORDS = 8          # LANCET_HAP_HEADER_WORDS: a haplotype of n bases takes this + (n + 15) // 16 words of its window's buffer
 HAP_UNALIGNED, HAP_IS_REF = 1, 2
 HAP_HAS_COVERAGE = 4          # LANCET_HAP_HAS_COVERAGE: the entry carries its per-base coverages (lancet_engine_set_haplotype_coverage)
+HAP_HAS_SUPPORT = 8           # LANCET_HAP_HAS_SUPPORT: the entry carries the counts of the reads that fit it (lancet_engine_set_haplotype_support)
 HAP_W_NCIGAR = 7              # LANCET_HAP_W_NCIGAR: the header word that counts an entry's CIGAR words (lancet_engine_set_haplotype_alignments)
 HAP_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}      # LANCET_HAP_OP_*: BAM's codes, SAM's extended letters
 
@@ -117,6 +118,12 @@ def coverage_to_py(vals: np.ndarray, length: int, ref_len: int) -> dict:
     if v.size != 4 * (length + ref_len):          # (a haplotype of a run without the switch: none)
         return {"path": np.zeros((0, 4), np.uint16), "ref": np.zeros((0, 4), np.uint16)}
     return {"path": v[:4 * length].reshape(length, 4).copy(), "ref": v[4 * length:].reshape(ref_len, 4).copy()}
+
+
+def support_to_py(vals) -> dict:
+    """The eight counts of one haplotype as {"fit": [Tf, Tr, Nf, Nr], "alone": [Tf, Tr, Nf, Nr]}."""
+    v = [int(x) for x in vals]
+    return {"fit": v[:4], "alone": v[4:8]}
 
 
 def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:

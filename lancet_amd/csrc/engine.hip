@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "build_lds.h"
 #include "host_common.h"
+#include "hap_support.h"   // hap_support_kernel: the reads that fit each haplotype, counted after the batch's windows are through
 #include "select_host.h"
 
 // window_fat.hip
@@ -334,6 +335,10 @@ struct lancet_engine {
   uint32_t hap_words = 0;
   uint32_t hap_aln = 0;       // lancet_engine_set_haplotype_alignments: the next upload's entries carry their CIGAR words (EngineCaps::hap_aln)
   uint32_t hap_cov = 0;       // lancet_engine_set_haplotype_coverage: ... and their per-base coverages (EngineCaps::hap_cov)
+  uint32_t hap_sup = 0;       // lancet_engine_set_haplotype_support: ... and the counts of the reads that fit them (EngineCaps::hap_sup), within hap_mm mismatches
+  uint32_t hap_mm = 0, hap_mm_run = 0;      // (hap_mm_run: of the batch that is uploaded, as caps.hap_sup is)
+  hipEvent_t ev_sup0 = nullptr, ev_sup1 = nullptr;      // around the support kernel (created with the switch)
+  float ms_sup = 0;
   DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
   LcHapResult hap;
   float ms_hap = 0;
@@ -506,6 +511,8 @@ void lancet_engine_destroy(lancet_engine *e) {
   if (e->evf1) (void)hipEventDestroy(e->evf1);
   if (e->ev_ready) (void)hipEventDestroy(e->ev_ready);
   if (e->ev_svc) (void)hipEventDestroy(e->ev_svc);
+  if (e->ev_sup0) (void)hipEventDestroy(e->ev_sup0);      // (the haplotype capture's: around the support kernel)
+  if (e->ev_sup1) (void)hipEventDestroy(e->ev_sup1);
   if (e->stream3) (void)hipStreamDestroy(e->stream3);
   if (e->stream2) (void)hipStreamDestroy(e->stream2);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -560,6 +567,22 @@ int lancet_engine_set_haplotype_coverage(lancet_engine *e, int on) {
   if (e->uploaded && !e->ran) { e->err = "set_haplotype_coverage between an upload and its run"; return LANCET_E_STATE; }
   if (on != 0 && on != 1) { e->err = "set_haplotype_coverage: on is 0 or 1"; return LANCET_E_ARG; }
   e->hap_cov = (uint32_t)on;
+  return LANCET_OK;
+}
+
+// ... and the reads that fit each of them, counted by a kernel of its own behind the windows (hap_support.h).  Same rules again.
+int lancet_engine_set_haplotype_support(lancet_engine *e, int on, int max_mismatches) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotype_support while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotype_support between an upload and its run"; return LANCET_E_STATE; }
+  if (on != 0 && on != 1) { e->err = "set_haplotype_support: on is 0 or 1"; return LANCET_E_ARG; }
+  if (max_mismatches < 0 || max_mismatches > 255) { e->err = "set_haplotype_support: max_mismatches is 0 .. 255"; return LANCET_E_ARG; }
+  if (on && !e->ev_sup0) {
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipEventCreate(&e->ev_sup0));
+    HIPCHK(e, hipEventCreate(&e->ev_sup1));
+  }
+  e->hap_sup = (uint32_t)on; e->hap_mm = (uint32_t)max_mismatches;
   return LANCET_OK;
 }
 
@@ -639,6 +662,8 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   e->caps.hap_cap = e->caps2.hap_cap = e->hap_words;
   e->caps.hap_aln = e->caps2.hap_aln = e->hap_words ? e->hap_aln : 0u;
   e->caps.hap_cov = e->caps2.hap_cov = e->hap_words ? e->hap_cov : 0u;
+  e->caps.hap_sup = e->caps2.hap_sup = e->hap_words ? e->hap_sup : 0u;
+  e->hap_mm_run = e->hap_mm;
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
   e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
@@ -1276,7 +1301,7 @@ int lancet_engine_submit(lancet_engine *e) {
   e->ran = false;
   e->variants.clear(); e->blob.clear(); e->stats.clear(); e->evt_len.clear(); e->evt.clear(); e->variants_lr.clear(); e->bx_blob.clear();
   e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
-  e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear(); e->hap.cov_off.assign(1, 0u); e->hap.cov.clear();
+  e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear(); e->hap.cov_off.assign(1, 0u); e->hap.cov.clear(); e->hap.sup.clear(); e->ms_sup = 0;
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1469,6 +1494,17 @@ int lancet_engine_wait(lancet_engine *e) {
     }
     e->variants.erase(std::remove_if(e->variants.begin(), e->variants.end(), [&](const lancet_variant &v) { return e->stats[v.window].status < 0; }), e->variants.end());
   }
+  // ---- the reads that fit each haplotype: every window's entries are final now (a re-run window started its buffer over), reads and entries
+  // are resident; the counts go into the entries' own words, which the read-back below brings over with the rest
+  if (e->caps.hap_cap && e->caps.hap_sup) {
+    HIPCHK(e, hipEventRecord(e->ev_sup0, e->stream));
+    hipLaunchKernelGGL(hap_support_kernel, dim3((unsigned)e->n_windows), dim3(LC_SUP_WG), 0, e->stream, (const DevBatch *)e->d_batch.p, (const uint32_t *)e->d_haplen.p,
+                       (uint32_t *)e->d_hap.p, e->caps.hap_cap, e->hap_mm_run, e->n_windows);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->ev_sup1, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipEventElapsedTime(&e->ms_sup, e->ev_sup0, e->ev_sup1));
+  }
   if (e->caps.hap_cap) { const int rc = lc_read_haplotypes(e); if (rc) return rc; }
   e->ran = true;
   return LANCET_OK;
@@ -1536,6 +1572,14 @@ int lancet_engine_results_haplotype_coverage(lancet_engine *e, const uint32_t **
   if (n_cov) *n_cov = (uint32_t)e->hap.cov.size();
   return LANCET_OK;
 }
+int lancet_engine_results_haplotype_support(lancet_engine *e, const uint32_t **support) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  if (support) *support = (e->hap.sup.size() == (size_t)HP_SUP_WORDS * e->hap.h.size() && !e->hap.sup.empty()) ? e->hap.sup.data() : nullptr;
+  return LANCET_OK;
+}
+// HIP-event milliseconds of the support kernel in the last run; 0 with the switch off
+float lancet_engine_haplotype_support_ms(const lancet_engine *e) { return e ? e->ms_sup : 0.f; }
 // milliseconds the last run's read-back of the haplotypes took on the host clock (lengths, compaction, copy, parsing); 0 with the capture off
 float lancet_engine_haplotype_readback_ms(const lancet_engine *e) { return e ? e->ms_hap : 0.f; }
 

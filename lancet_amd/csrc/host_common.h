@@ -182,6 +182,7 @@ static inline EngineCaps lc_caps_for_sizes(const LcBatchSizes &bs, const lancet_
   c.hap_cap = lc_emu_hap_sink.cap;                            // (the engine sets it from lancet_engine_set_haplotypes)
   c.hap_aln = lc_emu_hap_sink.cap ? lc_emu_hap_sink.aln : 0u; // (... and from lancet_engine_set_haplotype_alignments)
   c.hap_cov = lc_emu_hap_sink.cap ? lc_emu_hap_sink.cov : 0u; // (... and from lancet_engine_set_haplotype_coverage)
+  c.hap_sup = lc_emu_hap_sink.cap ? lc_emu_hap_sink.sup : 0u; // (... and from lancet_engine_set_haplotype_support)
   // settled windows: off unless the emulation is told otherwise, and then by the engine's rule (engine.hip lc_upload_caps: no trace, no capture, no linked reads)
   { const char *sv = getenv("LANCET_EMU_SETTLE"); const char *co = getenv("LANCET_SETTLE_CHAIN_ONLY");
     c.settle = (sv && atoi(sv) == 1 && !evt_cap && !c.hap_cap && !c.lr_mode) ? ((co && atoi(co) != 0) ? 2u : 1u) : 0u; }
@@ -201,13 +202,14 @@ static inline uint32_t lc_hap_used(uint32_t len_word, uint32_t cap, int32_t stat
 // cov_off / cov: lancet_engine_results_haplotype_coverage -- haplotype i's 16-bit counts are cov[cov_off[i] .. cov_off[i + 1]): 4 per path base, then 4 per
 // base of the stretch (none without EngineCaps::hap_cov)
 struct LcHapResult { std::vector<lancet_haplotype> h; std::vector<uint32_t> words; std::vector<uint8_t> truncated; std::vector<uint32_t> cigar_off{0u}, cigar;
-                     std::vector<uint32_t> cov_off{0u}; std::vector<uint16_t> cov; };
+                     std::vector<uint32_t> cov_off{0u}; std::vector<uint16_t> cov;
+                     std::vector<uint32_t> sup; /* lancet_engine_results_haplotype_support: 8 per haplotype (fit Tf Tr Nf Nr, alone Tf Tr Nf Nr), none without EngineCaps::hap_sup */ };
 // len_word[w]: DevOut::hap_len as the run left it; dense: the used words of the windows one behind the other (window w's start at off[w],
 // off[w + 1] - off[w] == lc_hap_used of it).
 static inline void lc_hap_collect(int n_windows, const uint32_t *len_word, const uint32_t *off, const uint32_t *dense, const lancet_window_stats *stats, LcHapResult *r) {
   r->h.clear(); r->words.clear(); r->truncated.assign((size_t)(n_windows > 0 ? n_windows : 0), 0);
   r->cigar_off.assign(1, 0u); r->cigar.clear();
-  r->cov_off.assign(1, 0u); r->cov.clear();
+  r->cov_off.assign(1, 0u); r->cov.clear(); r->sup.clear();
   for (int w = 0; w < n_windows; ++w) {
     if (stats[w].status < 0) continue;
     r->truncated[(size_t)w] = (len_word[w] & HP_TRUNC) ? 1 : 0;
@@ -221,6 +223,9 @@ static inline void lc_hap_collect(int n_windows, const uint32_t *len_word, const
       // ... and the coverage words behind those (LANCET_HAP_HAS_COVERAGE): two per base of path and stretch, each a pair of 16-bit counts, low half first
       const uint32_t nv = (e[HP_W_FLAGS] & LANCET_HAP_HAS_COVERAGE) ? 2u * (e[HP_W_LEN] + e[HP_W_REFLEN]) : 0u;
       if (nv > used - at - HP_HDR - nw - nc) break;
+      // ... and the eight support words behind those (LANCET_HAP_HAS_SUPPORT)
+      const uint32_t ns = (e[HP_W_FLAGS] & LANCET_HAP_HAS_SUPPORT) ? HP_SUP_WORDS : 0u;
+      if (ns > used - at - HP_HDR - nw - nc - nv) break;
       lancet_haplotype x; memset(&x, 0, sizeof(x));
       x.window = w; x.index_in_window = idx++; x.kmer = (uint16_t)(e[HP_W_KC] & 0xFFFFu); x.component = (uint16_t)(e[HP_W_KC] >> 16);
       x.ref_off = e[HP_W_REFOFF]; x.ref_len = e[HP_W_REFLEN]; x.len = e[HP_W_LEN]; x.word_off = (uint32_t)r->words.size();
@@ -230,8 +235,9 @@ static inline void lc_hap_collect(int n_windows, const uint32_t *len_word, const
       r->cigar_off.push_back((uint32_t)r->cigar.size());
       if (nv) { const size_t o = r->cov.size(); r->cov.resize(o + 2u * (size_t)nv); memcpy(r->cov.data() + o, e + HP_HDR + nw + nc, sizeof(uint32_t) * (size_t)nv); }      // (little-endian host: a word is its two counts in order)
       r->cov_off.push_back((uint32_t)r->cov.size());
+      r->sup.insert(r->sup.end(), e + HP_HDR + nw + nc + nv, e + HP_HDR + nw + nc + nv + ns);
       r->h.push_back(x);
-      at += HP_HDR + nw + nc + nv;
+      at += HP_HDR + nw + nc + nv + ns;
     }
   }
 }

@@ -5509,6 +5509,29 @@ DEVNI void hap_cov(Ctx &c, int m) {
   }
   WG_LANE0 { p[HP_W_FLAGS] |= LANCET_HAP_HAS_COVERAGE; }
 }
+// ... and room for the reads that fit it (EngineCaps::hap_sup), behind the coverage words: HP_SUP_WORDS zeroed words, fit and alone by class
+// Tf Tr Nf Nr.  The window kernels only reserve them -- which reads fit a path is known once all its rivals are, so the support kernel
+// (hap_support.h) counts after the batch's windows are through.  Lane 0, once per path behind hap_cigar / hap_cov: what it reads of the entry
+// it wrote itself or they wrote in front of a barrier.  Words that do not fit mark the window HP_TRUNC.  The entry says LANCET_HAP_HAS_SUPPORT.
+DEVNI void hap_sup(Ctx &c) {
+  LC_WS &S = LC_SREF(c);
+  WG_LANE0 {
+    const uint32_t cap = LC_CTX(c).C->hap_cap;
+    LC_GLOBAL uint32_t *lenp = LC_HAP_LEN(c) + S.w;
+    const uint32_t cur = ld2(lenp);
+    if (!(cur & HP_TRUNC)) {
+      LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)S.w * cap + cur;
+      const uint32_t ncov = (p[HP_W_FLAGS] & LANCET_HAP_HAS_COVERAGE) ? 2u * (p[HP_W_LEN] + p[HP_W_REFLEN]) : 0u;
+      const uint32_t used = cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG] + ncov;
+      if (used > cap || HP_SUP_WORDS > cap - used) st2(lenp, cur | HP_TRUNC);
+      else {
+        LC_GLOBAL uint32_t *q = LC_HAP_OUT(c) + (size_t)S.w * cap + used;
+        for (uint32_t i = 0; i < HP_SUP_WORDS; ++i) q[i] = 0u;
+        p[HP_W_FLAGS] |= LANCET_HAP_HAS_SUPPORT;
+      }
+    }
+  }
+}
 // lane 0, after the path's walk: the records it emitted, and the entry counts
 DEV void hap_close(Ctx &c) {
   LC_WS &S = LC_SREF(c);
@@ -5519,7 +5542,8 @@ DEV void hap_close(Ctx &c) {
   LC_GLOBAL uint32_t *p = LC_HAP_OUT(c) + (size_t)S.w * cap + cur;
   p[HP_W_NVAR] = (uint32_t)S.emit_seq - p[HP_W_FIRST];
   const uint32_t ncov = (p[HP_W_FLAGS] & LANCET_HAP_HAS_COVERAGE) ? 2u * (p[HP_W_LEN] + p[HP_W_REFLEN]) : 0u;      // (hap_cov's words, behind the CIGAR's)
-  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG] + ncov);
+  const uint32_t nsup = (p[HP_W_FLAGS] & LANCET_HAP_HAS_SUPPORT) ? HP_SUP_WORDS : 0u;                             // (hap_sup's, behind those)
+  st2(lenp, cur + HP_HDR + (p[HP_W_LEN] + 15u) / 16u + p[HP_W_NCIG] + ncov + nsup);
 }
 
 // eka (reference src/Graph.cc:1430-1501) via countRefPath (:2420-2445)
@@ -5529,6 +5553,7 @@ DEVNI void count_ref_path(Ctx &c) {
   const bool hap_on = wg_uniform((int)LC_CTX(c).C->hap_cap) != 0;      // (haplotype capture: the one test of a run without it)
   const bool hap_aln = hap_on && wg_uniform((int)LC_CTX(c).C->hap_aln) != 0;      // (... with the CIGARs: read with the capture on only)
   const bool hap_cvg = hap_on && wg_uniform((int)LC_CTX(c).C->hap_cov) != 0;      // (... with the per-base coverages: likewise)
+  const bool hap_spt = hap_on && wg_uniform((int)LC_CTX(c).C->hap_sup) != 0;      // (... with room for the read support: likewise)
   if (wg_bcastu(&S.sink) != LC_NIL) {
     WG_LANE0 { evt(c, EV_SEARCH, (uint32_t)W.gr[S.source].comp); S.tmp0 = S.tmp1 = S.tmp2 = 0; S.part[0] = 0; S.part[1] = 0; S.part[2] = 0; S.part[3] = 0; S.pc_i = 0; S.pc_rd = 0; }
     const bool replay = wg_bcast(&S.pc_ok) != 0;             // the paths are the ones findRepeatsInGraphPaths found (pcache_store)
@@ -5612,6 +5637,8 @@ DEVNI void count_ref_path(Ctx &c) {
       if (hap_aln && !wg_bcast(&S.overflow)) hap_cigar(c, (int)wg_bcastu(&S.part[5]), hd, (int)wg_bcastu(&S.part[7]));
       // ... and its coverages behind that: pdesc and refcov are what the walk is about to read, whether the path is new or replayed, differs or not
       if (hap_cvg && !wg_bcast(&S.overflow)) hap_cov(c, (int)wg_bcastu(&S.part[5]));
+      // ... and the words the support kernel counts into, behind those
+      if (hap_spt && !wg_bcast(&S.overflow)) hap_sup(c);
       PHASE(c, 14);
       if (hd == 0 && !old_walk) {
         SUBPHASE(c, 4, 7);

@@ -39,6 +39,11 @@
 // (lancet_engine_set_haplotype_coverage; the alignments are turned on with it, the table needs the columns).  Alone or with the other two;
 // the same rules; the buffer is 2 * (2 * longest + --max-indel-len + 256) words per path larger.  With --haplotype-sam every SAM record
 // gains the tags nf nr tf tr (B:S): the path's an+ an- at+ at-, one value per SEQ base.
+// --haplotype-support FILE: per haplotype, in the same order, one line: the --haplotypes header up to ref=off+len without the '>', a tab, and
+// the eight counts of lancet_engine_set_haplotype_support tab-separated -- the reads that fit the path (fit_tf fit_tr fit_nf fit_nr) and
+// that fit it alone among the paths of its (k, component) (alone_tf ... alone_nr), within --haplotype-support-mismatches N (default 5, the
+// reference's HD_DISTANCE_CUTOFF) mismatches of an ungapped placement; the first line names the columns.  Alone or with the other three; the
+// same rules; the buffer is 8 words per path larger.  With --haplotype-sam every SAM record gains the tags sf and sa (B:I, four values each).
 #include "../../include/lancet_host.h"
 #include "../../include/lancet_gather.h"
 
@@ -71,7 +76,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"haplotype-support", 0, 1}, {"haplotype-support-mismatches", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -89,6 +94,8 @@ uint32_t hap_words_for(uint32_t longest, int max_indel_len) {
 uint32_t hap_cigar_words() { return MV_PATHS * 64u; }
 // --haplotype-coverage: two words per base of every path and of its stretch (four 16-bit counts each)
 uint32_t hap_cov_words(uint32_t longest, int max_indel_len) { return MV_PATHS * 2u * (2u * longest + (uint32_t)max_indel_len + 256u); }
+// --haplotype-support: eight words per path
+uint32_t hap_sup_words() { return MV_PATHS * 8u; }
 // --haplotype-sam: (name, length) of the contigs of a FASTA file in its order -- from its .fai when there is one, else from the file itself
 bool fasta_contigs(const std::string &path, std::vector<std::pair<std::string, long>> *out) {
   out->clear();
@@ -147,6 +154,10 @@ void usage() {
         "                                       alone or with --haplotypes, same rules\n"
         "   --haplotype-coverage <file>       : per haplotype its header line and the reference's -v table of per-base coverages (Pos r p d an+ an- at+ at-\n"
         "                                       rn+ rn- rt+ rt-); alone or with the other two, same rules; adds the tags nf nr tf tr to --haplotype-sam\n"
+        "   --haplotype-support <file>        : per haplotype one line: its header and the reads that fit it / fit it alone among the paths of its k and\n"
+        "                                       component, by class (fit_tf fit_tr fit_nf fit_nr alone_tf ...); alone or with the other three, same rules;\n"
+        "                                       adds the tags sf sa to --haplotype-sam\n"
+        "   --haplotype-support-mismatches <n>: mismatches an ungapped placement of a read on a path may have, 0 .. 255 [default: 5]\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -161,7 +172,8 @@ int main(int argc, char **argv) {
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
-  std::string rendezvous, hap_file, sam_file, cov_file;
+  std::string rendezvous, hap_file, sam_file, cov_file, sup_file;
+  int sup_mm = 5;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -192,6 +204,7 @@ int main(int argc, char **argv) {
     else if (L == "linked-reads") ho.linked = 1; else if (L == "kmer-recovery") kmer_recovery = 1; else if (L == "primary-alignment-only") ho.primary_alignment_only = 1; else if (L == "XA-tag-filter") ho.xa_filter = 1;
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
     else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v; else if (L == "haplotype-coverage") cov_file = v;
+    else if (L == "haplotype-support") sup_file = v; else if (L == "haplotype-support-mismatches") sup_mm = atoi(v);
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -201,6 +214,8 @@ int main(int argc, char **argv) {
   if (!hap_file.empty() && ranks > 1) return die("--haplotypes is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (!sam_file.empty() && ranks > 1) return die("--haplotype-sam is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (!cov_file.empty() && ranks > 1) return die("--haplotype-coverage is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (!sup_file.empty() && ranks > 1) return die("--haplotype-support is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (sup_mm < 0 || sup_mm > 255) return die("--haplotype-support-mismatches must be 0 .. 255");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -317,12 +332,15 @@ int main(int argc, char **argv) {
   }
   FILE *cov_out = nullptr;
   if (!cov_file.empty() && !(cov_out = fopen(cov_file.c_str(), "w"))) return die("cannot write " + cov_file);
-  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr;
+  FILE *sup_out = nullptr;
+  if (!sup_file.empty() && !(sup_out = fopen(sup_file.c_str(), "w"))) return die("cannot write " + sup_file);
+  if (sup_out) fputs("#haplotype\tfit_tf\tfit_tr\tfit_nf\tfit_nr\talone_tf\talone_tr\talone_nf\talone_nr\n", sup_out);
+  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr, sup_on = sup_out != nullptr;
   const bool aln_on = sam_on || cov_on;                  // the table is laid out by the alignment's columns
-  const bool hap_on = hap_out != nullptr || aln_on;      // any of the files turns the capture on; the SAM and the coverage one the alignments as well
-  auto hap_extra_for = [&](uint32_t longest) -> uint32_t { return (aln_on ? hap_cigar_words() : 0u) + (cov_on ? hap_cov_words(longest, max_indel_len) : 0u); };
+  const bool hap_on = hap_out != nullptr || aln_on || sup_on;      // any of the files turns the capture on; the SAM and the coverage one the alignments as well
+  auto hap_extra_for = [&](uint32_t longest) -> uint32_t { return (aln_on ? hap_cigar_words() : 0u) + (cov_on ? hap_cov_words(longest, max_indel_len) : 0u) + (sup_on ? hap_sup_words() : 0u); };
   long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
-  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::string hapsup; /* --haplotype-support: its lines */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
@@ -379,6 +397,8 @@ int main(int argc, char **argv) {
       if (aln_on && lancet_engine_results_haplotype_alignments(sl.e, &cig_off, &cig, &ncig) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       const uint32_t *cov_off = nullptr; const uint16_t *cov = nullptr; uint32_t ncov = 0;
       if (cov_on && lancet_engine_results_haplotype_coverage(sl.e, &cov_off, &cov, &ncov) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+      const uint32_t *sup = nullptr;
+      if (sup_on && lancet_engine_results_haplotype_support(sl.e, &sup) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
       for (uint32_t i = 0; i < nh; ++i) {
         const lancet_haplotype &x = hp[i];
@@ -421,7 +441,17 @@ int main(int argc, char **argv) {
             j.hapsam += q == 0 ? "\tnf:B:S" : q == 1 ? "\tnr:B:S" : q == 2 ? "\ttf:B:S" : "\ttr:B:S";
             for (uint32_t b = 0; b < x.len; ++b) { j.hapsam += ','; j.hapsam += std::to_string((unsigned)pcv[4u * b + (uint32_t)q]); }
           }
+          if (sup) for (int q = 0; q < 2; ++q) {           // --haplotype-support as well: fit and alone, Tf Tr Nf Nr
+            j.hapsam += q == 0 ? "\tsf:B:I" : "\tsa:B:I";
+            for (int c = 0; c < 4; ++c) { j.hapsam += ','; j.hapsam += std::to_string(sup[8u * (size_t)i + 4u * (uint32_t)q + (uint32_t)c]); }
+          }
           j.hapsam += '\n';
+        }
+        if (sup_on) {
+          snprintf(head, sizeof head, "%s|k=%u|comp=%u|path=%d|ref=%u+%u", hdr, (unsigned)x.kmer, (unsigned)x.component, x.index_in_window, x.ref_off, x.ref_len);
+          j.hapsup += head;
+          for (int c = 0; c < 8; ++c) { j.hapsup += '\t'; j.hapsup += std::to_string(sup ? sup[8u * (size_t)i + (uint32_t)c] : 0u); }
+          j.hapsup += '\n';
         }
         if (cov_on) {
           // the reference's table (printVerticalAlignment): Pos is the path index and stays on a deletion column; the side with a gap has empty cells
@@ -461,6 +491,7 @@ int main(int argc, char **argv) {
       if (!j.trace.empty()) fputs(j.trace.c_str(), stderr);
       if (!j.hapfa.empty() && fwrite(j.hapfa.data(), 1, j.hapfa.size(), hap_out) != j.hapfa.size()) { fail = "cannot write " + hap_file; return false; }
       if (!j.hapsam.empty() && fwrite(j.hapsam.data(), 1, j.hapsam.size(), sam_out) != j.hapsam.size()) { fail = "cannot write " + sam_file; return false; }
+      if (!j.hapsup.empty() && fwrite(j.hapsup.data(), 1, j.hapsup.size(), sup_out) != j.hapsup.size()) { fail = "cannot write " + sup_file; return false; }
       if (!j.hapcov.empty() && fwrite(j.hapcov.data(), 1, j.hapcov.size(), cov_out) != j.hapcov.size()) { fail = "cannot write " + cov_file; return false; }
       int arc = LANCET_OK;
       if (ranked) {                                  // the records travel: keyed, reduced, window numbers of the whole tiling
@@ -534,7 +565,8 @@ int main(int argc, char **argv) {
           for (int32_t i = 0; i < SL.n_windows; ++i) longest = std::max(longest, SL.ref_off[i + 1] - SL.ref_off[i]);
           if (more_verbose && lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
           if (hap_on && (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
-                         lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK))
+                         lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK ||
+                         lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK))
             return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
         }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
@@ -568,7 +600,7 @@ int main(int argc, char **argv) {
       for (int32_t w = 0; w < nk; ++w) longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]);
       if (cov_on && !more_verbose) { sl.raw.assign((size_t)nk, std::string()); for (int32_t w = 0; w < nk; ++w) sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
       if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
-          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK)
+          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK || lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK)
         return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
@@ -612,8 +644,12 @@ int main(int argc, char **argv) {
       if (fclose(cov_out) != 0) return die("cannot write " + cov_file);
       fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, cov_file.c_str());
     }
+    if (sup_on) {
+      if (fclose(sup_out) != 0) return die("cannot write " + sup_file);
+      fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, sup_file.c_str());
+    }
     if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
-                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_file.c_str());
+                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_on ? cov_file.c_str() : sup_file.c_str());
   }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
@@ -660,7 +696,8 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc; ++i) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
-    if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0 || strcmp(argv[i], "--haplotype-coverage") == 0) { ++i; continue; }  // (a second output of the same run)
+    if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0 || strcmp(argv[i], "--haplotype-coverage") == 0 ||
+        strcmp(argv[i], "--haplotype-support") == 0 || strcmp(argv[i], "--haplotype-support-mismatches") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

@@ -134,6 +134,8 @@ struct EngineCaps {
   uint32_t hap_aln;      /* ... with every entry's CIGAR words behind its path words (lancet_engine_set_haplotype_alignments); read only where hap_cap != 0 */
   uint32_t hap_cov;      /* ... with every base's read support behind the CIGAR words: 2 * (len + ref_len) words, the entry flagged LANCET_HAP_HAS_COVERAGE
                             (lancet_engine_set_haplotype_coverage; kernels.h hap_cov); read only where hap_cap != 0 */
+  uint32_t hap_sup;      /* ... with eight zeroed words behind those for the reads that fit the path (fit[4], alone[4] by class Tf Tr Nf Nr), the entry flagged
+                            LANCET_HAP_HAS_SUPPORT (lancet_engine_set_haplotype_support; kernels.h hap_sup reserves, hap_support.h counts); read only where hap_cap != 0 */
   uint32_t settle;       /* the build kernel may settle reference-only windows (PreHdr::settled): set by the engine when nothing is on that wants to
                             see such a window's graph -- trace, haplotype capture, linked reads -- and LANCET_NO_SETTLE is not set.  1: the reference chain beside components without a source
                              ; 2: the chain has to be the whole graph (LANCET_SETTLE_CHAIN_ONLY=1) */
@@ -147,10 +149,14 @@ struct EngineCaps {
  * With EngineCaps::hap_cov the coverages follow behind those, and LANCET_HAP_HAS_COVERAGE in HP_W_FLAGS says so: two words per path base
  * (an+ | an- << 16, at+ | at- << 16), HP_W_LEN of them, then two per base of the stretch (rn+ | rn- << 16, rt+ | rt- << 16), HP_W_REFLEN of
  * them -- the 16-bit counts the kernels hold, the cells of a row of the reference's vertical alignment (kernels.h hap_cov).
+ * With EngineCaps::hap_sup HP_SUP_WORDS words follow behind those, and LANCET_HAP_HAS_SUPPORT says so: fit Tf Tr Nf Nr, alone Tf Tr Nf Nr.  The
+ * window kernels leave them 0; the support kernel (hap_support.h) counts into them once the window's entries are final.  The entries of one
+ * (k, component) lie one behind the other: a window visits each k once and each component of it once.
  * DevOut::hap_len[w] holds the words of the window's CLOSED entries: the entry of the path being walked lies behind them and counts
  * once its walk is through (kernels.h hap_open / hap_close).  HP_TRUNC in that word: an entry did not fit, nothing is written after it. */
 #define HP_HDR 8u
 #define HP_TRUNC 0x80000000u
+#define HP_SUP_WORDS 8u
 enum { HP_W_KC = 0,        /* k | component << 16                                                      */
        HP_W_REFOFF, HP_W_REFLEN,   /* Ref_t::seq as (offset into the window reference, length)         */
        HP_W_LEN,           /* bases of the path string                                                 */
@@ -423,8 +429,8 @@ struct DevOut {
 /* Host emulation of the kernels only: where the haplotype capture writes and how large a window's buffer is.  The emulator's driver
  * fills a DevOut of its own; a test build that wants the capture sets this before the run (tests/hap_emu), lc_caps_for_sizes and the
  * kernels read it in place of DevOut::hap_len / hap_out. */
-struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; uint32_t aln; /* EngineCaps::hap_aln of the run */ uint32_t cov; /* ... and its hap_cov */ };
-inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr, 0u, 0u};
+struct LcEmuHapSink { uint32_t cap; uint32_t *len, *out; uint32_t aln; /* EngineCaps::hap_aln of the run */ uint32_t cov; /* ... and its hap_cov */ uint32_t sup; /* ... and its hap_sup */ };
+inline thread_local LcEmuHapSink lc_emu_hap_sink = {0u, nullptr, nullptr, 0u, 0u, 0u};
 #define LC_HAP_LEN(c) (lc_emu_hap_sink.len)
 #define LC_HAP_OUT(c) (lc_emu_hap_sink.out)
 #else

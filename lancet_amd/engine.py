@@ -80,6 +80,10 @@ def lib():
         L.lancet_engine_results_haplotype_alignments.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lancet_engine_set_haplotype_coverage.argtypes = [C.c_void_p, C.c_int]
         L.lancet_engine_results_haplotype_coverage.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_uint32)]
+        L.lancet_engine_set_haplotype_support.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.lancet_engine_results_haplotype_support.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32))]
+        L.lancet_engine_haplotype_support_ms.restype = C.c_float
+        L.lancet_engine_haplotype_support_ms.argtypes = [C.c_void_p]
         L.lancet_engine_haplotype_readback_ms.restype = C.c_float
         L.lancet_engine_haplotype_readback_ms.argtypes = [C.c_void_p]
         L.lancet_engine_set_trace_level.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
@@ -158,12 +162,15 @@ class DeviceReads:
 
 class Engine:
     def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1, haplotype_words: int = 0,
-                 haplotype_alignments: bool = False, haplotype_coverage: bool = False):
+                 haplotype_alignments: bool = False, haplotype_coverage: bool = False, haplotype_support: bool = False,
+                 haplotype_support_mismatches: int = 5):
         """trace_words: 32-bit words of trace events kept per window (0: no trace).  trace_level 1: the reference's -v lines; 2: its -V
         (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level).
         haplotype_words: 32-bit words kept per window for its assembled haplotypes (0: none; lancet_engine_set_haplotypes, haplotypes()).
         haplotype_alignments: each of them with its CIGAR against its reference stretch, out of the same words (set_haplotype_alignments).
-        haplotype_coverage: each of them with the reads' support of every base of path and stretch, out of the same words (set_haplotype_coverage)."""
+        haplotype_coverage: each of them with the reads' support of every base of path and stretch, out of the same words (set_haplotype_coverage).
+        haplotype_support: each of them with the numbers of reads that fit it, and fit it alone among the haplotypes of its (k, component), within
+        haplotype_support_mismatches mismatches, by class Tf Tr Nf Nr; eight more words each (set_haplotype_support)."""
         self.L = lib()
         self.params = params or abi.default_params()
         h = C.c_void_p()
@@ -186,6 +193,9 @@ class Engine:
             self.set_haplotype_alignments(True)
         if haplotype_coverage:
             self.set_haplotype_coverage(True)
+        self._hap_sup = False
+        if haplotype_support:
+            self.set_haplotype_support(True, haplotype_support_mismatches)
 
     def set_haplotypes(self, words_per_window: int) -> None:
         """lancet_engine_set_haplotypes: for the uploads that follow (0: off).  EngineError between an upload and its run."""
@@ -203,11 +213,22 @@ class Engine:
         self._chk(self.L.lancet_engine_set_haplotype_coverage(self.h, 1 if on else 0))
         self._hap_cov = bool(on)
 
+    def set_haplotype_support(self, on: bool, max_mismatches: int = 5) -> None:
+        """lancet_engine_set_haplotype_support: for the uploads that follow; nothing while the capture is off.  EngineError between an
+        upload and its run, and for max_mismatches outside 0 .. 255."""
+        self._chk(self.L.lancet_engine_set_haplotype_support(self.h, 1 if on else 0, int(max_mismatches)))
+        self._hap_sup = bool(on)
+
+    def haplotype_support_ms(self) -> float:
+        """HIP-event milliseconds of the support kernel in the last run (0 with the switch off)."""
+        return float(self.L.lancet_engine_haplotype_support_ms(self.h))
+
     def haplotypes(self):
         """(haplotypes, truncated) of the last run: abi.haplotypes_to_py's dicts ordered by (window, index), and per window 1 where some of its
         haplotypes did not fit.  Both empty / all zero with the capture off.  With haplotype_alignments every dict also has "cigar": (length, op)
         pairs, op one of = X I D (I: bases the reference stretch does not have).  With haplotype_coverage every dict has "cov": {"path": len x 4
-        uint16 (an+ an- at+ at-), "ref": ref_len x 4 uint16 (rn+ rn- rt+ rt-)}, the cells of the reference's vertical alignment."""
+        uint16 (an+ an- at+ at-), "ref": ref_len x 4 uint16 (rn+ rn- rt+ rt-)}, the cells of the reference's vertical alignment.  With
+        haplotype_support every dict has "support": {"fit": [Tf, Tr, Nf, Nr], "alone": [Tf, Tr, Nf, Nr]}, the reads that fit it (include/lancet_engine.h)."""
         hp, n, wp, nwd, tp = C.POINTER(abi.LancetHaplotype)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint8)()
         self._chk(self.L.lancet_engine_results_haplotypes(self.h, C.byref(hp), C.byref(n), C.byref(wp), C.byref(nwd), C.byref(tp)))
         words = np.ctypeslib.as_array(wp, shape=(nwd.value,)).copy() if nwd.value else np.zeros(0, np.uint32)
@@ -224,6 +245,11 @@ class Engine:
             vals = np.ctypeslib.as_array(vp, shape=(nv.value,)).copy() if nv.value else np.zeros(0, np.uint16)
             for i, h in enumerate(haps):
                 h["cov"] = abi.coverage_to_py(vals[op[i]:op[i + 1]], h["len"], h["ref_len"])
+        if self._hap_sup:
+            sp = C.POINTER(C.c_uint32)()
+            self._chk(self.L.lancet_engine_results_haplotype_support(self.h, C.byref(sp)))
+            for i, h in enumerate(haps):
+                h["support"] = abi.support_to_py(sp[8 * i:8 * i + 8] if sp else [0] * 8)
         return haps, [int(tp[w]) for w in range(nw)]
 
     def haplotype_readback_ms(self) -> float:
