@@ -406,6 +406,41 @@ int lancet_engine_results_haplotype_coverage(lancet_engine *e, const uint32_t **
 int lancet_engine_set_haplotype_support(lancet_engine *e, int on, int max_mismatches);
 int lancet_engine_results_haplotype_support(lancet_engine *e, const uint32_t **support /* [n][8]: fit Tf Tr Nf Nr, alone Tf Tr Nf Nr */);
 float lancet_engine_haplotype_support_ms(const lancet_engine *e);
+/* ---- ... and, per read, where it lies on the haplotype it fits best ----
+ * lancet_engine_set_haplotype_placements(e, 1, max_mismatches): after the windows of the runs that follow are through, a second kernel of
+ * that kind writes one record per read of the batch.  The reference has no such value; this is its definition, in the terms of the support
+ * definition above (the read as the kernels see it: trimmed, t bases, in BAM orientation; a placement on a whole entry h of M bases at its k
+ * is an offset o in [k - t, M - k], at least k bases of overlap; mm(o) the overlap positions that differ; d(r, h) the smallest mm(o) on h).
+ * Over ALL whole entries of the read's window:
+ *   mismatches   = the smallest d;
+ *   haplotype    = the entry with that d that has the smallest index_in_window;
+ *   offset       = the smallest o on that entry with mm(o) = d (negative: the read's first -o bases hang over the path's start);
+ *   n_offsets    = how many offsets of that entry have mm(o) = d;
+ *   n_haplotypes = how many entries of the window have that d -- across all (k, component) groups, so the same string reported at two k
+ *                  counts twice, as it does in the support counts.
+ * Both counts saturate at LANCET_PLACEMENT_COUNT_MAX.  A read is PLACED iff such an entry exists and mismatches <= max_mismatches; a read
+ * that is not has haplotype = -1 and every other field 0: t < k for every entry, a junk read, a window without whole entries, a
+ * window with status < 0.  In a truncated window the candidates are its whole entries; a window the second tier re-ran has that tier's.
+ * The entry with the smallest d of the window has the smallest d of its own group: with equal limits a placed read FITS its haplotype in the
+ * sense of lancet_engine_set_haplotype_support.
+ * on is 0 or 1, max_mismatches 0..255 (else LANCET_E_ARG), independent of the support limit; the state rules are those of
+ * lancet_engine_set_haplotype_support; without the capture itself the switch does nothing.  The records lie in a buffer of their own: no
+ * entry changes, and neither switch changes the other's output.  A window's buffer that could hold more than 2^24 - 1 entries
+ * (words_per_window above 9 * (2^24 - 1)) or parameters whose longest path (1024 + max_indel_len + 256 bases) is not below 2^17 bases are
+ * refused with LANCET_E_ARG where the switch is set, and by lancet_engine_set_haplotypes while it is on.
+ * lancet_engine_results_haplotype_placements: after a run, p[read_begin[w] .. read_begin[w + 1]) are the reads of window w in the
+ * batch's read order, tlen[i] the trimmed length t the kernel used for read i (a caller tells soft clips from overlap by it).  p is NULL
+ * and n_reads 0 with the switch off.  lancet_engine_haplotype_placement_ms: HIP-event milliseconds of the kernel in the last run. */
+#define LANCET_PLACEMENT_COUNT_MAX 127u
+typedef struct lancet_read_placement {
+  int32_t haplotype;      /* index_in_window, -1: not placed */
+  int32_t offset;
+  uint16_t mismatches, n_offsets, n_haplotypes, cls;   /* cls 0..3 = Tf Tr Nf Nr */
+} lancet_read_placement;
+int   lancet_engine_set_haplotype_placements(lancet_engine *e, int on, int max_mismatches);   /* 0..255 */
+int   lancet_engine_results_haplotype_placements(lancet_engine *e, const lancet_read_placement **p, uint32_t *n_reads,
+                                                 const uint32_t **read_begin /* [n_windows + 1] */, const uint16_t **tlen);
+float lancet_engine_haplotype_placement_ms(const lancet_engine *e);
 
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */

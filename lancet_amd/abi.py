@@ -126,6 +126,59 @@ def support_to_py(vals) -> dict:
     return {"fit": v[:4], "alone": v[4:8]}
 
 
+class LancetReadPlacement(C.Structure):
+    """lancet_read_placement: where one read lies on the haplotype it fits best (lancet_engine_results_haplotype_placements)."""
+    _fields_ = [("haplotype", C.c_int32), ("offset", C.c_int32), ("mismatches", C.c_uint16), ("n_offsets", C.c_uint16),
+                ("n_haplotypes", C.c_uint16), ("cls", C.c_uint16)]
+
+
+PLACEMENT_DTYPE = np.dtype([("haplotype", "<i4"), ("offset", "<i4"), ("mismatches", "<u2"), ("n_offsets", "<u2"), ("n_haplotypes", "<u2"), ("cls", "<u2")])
+PLACEMENT_COUNT_MAX = 127     # LANCET_PLACEMENT_COUNT_MAX: n_offsets and n_haplotypes saturate here
+
+
+def placements_to_py(pptr, n: int, read_begin_ptr, n_windows: int, tlen_ptr):
+    """(records, read_begin, tlen): the lancet_read_placement records as a numpy structured array (PLACEMENT_DTYPE) in the batch's read order,
+    read_begin[n_windows + 1] and the trimmed length of every read.  No records (a NULL pointer): three empty arrays but read_begin = [0]."""
+    if not pptr or not n:
+        return np.zeros(0, PLACEMENT_DTYPE), np.zeros(1, np.uint32), np.zeros(0, np.uint16)
+    assert C.sizeof(LancetReadPlacement) == PLACEMENT_DTYPE.itemsize
+    recs = np.frombuffer(C.string_at(pptr, n * PLACEMENT_DTYPE.itemsize), dtype=PLACEMENT_DTYPE).copy()
+    rb = np.ctypeslib.as_array(read_begin_ptr, shape=(n_windows + 1,)).copy()
+    tl = np.ctypeslib.as_array(tlen_ptr, shape=(n,)).copy()
+    return recs, rb, tl
+
+
+def read_cigar(o: int, t: int, length: int, ref_off: int, cigar) -> tuple:
+    """(start, [(n, op)], has_m): a placed read's alignment on the window reference through its haplotype's -- the rule of lc_read_cigar
+    (lancet_amd/csrc/host_common.h), restated column by column.  o, t: the placement's offset and the read's trimmed length; length, ref_off,
+    cigar: the haplotype's len, ref_off and (n, op_char) pairs (none: the path lies on its stretch base for base).  start is 0-based on the
+    window reference; ops are M I D S; has_m is False for a read that lies wholly inside an I run (start: the column behind the run)."""
+    cols, pp, rc = [], 0, 0          # one (op, path position or None, stretch column -- for an I the one behind it) per alignment column
+    for n, op in (cigar or [(length, "=")]):
+        for _ in range(n):
+            if op == "D":
+                cols.append(("D", None, rc))
+                rc += 1
+            else:
+                cols.append(("I" if op == "I" else "M", pp, rc))
+                pp += 1
+                rc += 0 if op == "I" else 1
+    a, b = max(0, o), min(length, o + t)
+    on_path = [i for i, c in enumerate(cols) if c[1] is not None and a <= c[1] < b]
+    kept = cols[on_path[0]:on_path[-1] + 1]            # (the D columns in between stay, those in front and behind go)
+    ops = [[a - o, "S"]]
+    for c in kept:
+        if ops[-1][1] == c[0]:
+            ops[-1][0] += 1
+        else:
+            ops.append([1, c[0]])
+    if ops[-1][1] == "S":
+        ops[-1][0] += o + t - b
+    else:
+        ops.append([o + t - b, "S"])
+    return ref_off + kept[0][2], [(n, op) for n, op in ops if n], any(c[0] == "M" for c in kept)
+
+
 def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:
     """lancet_haplotype records as dicts, `seq` = the path string (2 bits per base, first base in the low bits of a word)."""
     out = []

@@ -18,6 +18,7 @@
 #include "build_lds.h"
 #include "host_common.h"
 #include "hap_support.h"   // hap_support_kernel: the reads that fit each haplotype, counted after the batch's windows are through
+#include "hap_place.h"     // hap_placement_kernel: where each read lies on the haplotype it fits best, written at the same point
 #include "select_host.h"
 
 // window_fat.hip
@@ -339,6 +340,15 @@ struct lancet_engine {
   uint32_t hap_mm = 0, hap_mm_run = 0;      // (hap_mm_run: of the batch that is uploaded, as caps.hap_sup is)
   hipEvent_t ev_sup0 = nullptr, ev_sup1 = nullptr;      // around the support kernel (created with the switch)
   float ms_sup = 0;
+  uint32_t hap_place = 0, hap_place_run = 0;      // lancet_engine_set_haplotype_placements: one record per read from a kernel of its own (hap_place.h), within
+  uint32_t place_mm = 0, place_mm_run = 0;        // place_mm mismatches (the _run pair: of the batch that is uploaded)
+  hipEvent_t ev_pl0 = nullptr, ev_pl1 = nullptr;  // around the placement kernel (created with the switch)
+  float ms_place = 0;
+  DevBuf d_place;                                 // [n_reads * PL_WORDS], allocated by an upload with the switch on, zeroed per run
+  DevBatch h_db;                                  // the uploaded batch's device pointers (lc_upload_rest): read_begin and rinfo come back once per upload
+  bool place_meta = false;                        // ... and are here: place_rb, place_ri
+  std::vector<uint32_t> place_rb, place_ri, place_rec;
+  LcPlaceResult place;
   DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
   LcHapResult hap;
   float ms_hap = 0;
@@ -498,7 +508,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   DevBuf *all[] = {&e->d_params, &e->d_batch, &e->d_caps, &e->d_out, &e->d_works, &e->d_chr, &e->d_refstart, &e->d_refoff, &e->d_refasc,
                    &e->d_refcodes, &e->d_readbegin, &e->d_seqoff, &e->d_seq, &e->d_qual, &e->d_label, &e->d_strand, &e->d_mate, &e->d_mapped,
                    &e->d_rinfo, &e->d_name, &e->d_bw, &e->d_gw, &e->d_bases, &e->d_good, &e->d_variants, &e->d_blob, &e->d_counters,
-                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum, &e->d_haplen, &e->d_hap, &e->d_hapoff, &e->d_hapdense};
+                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum, &e->d_haplen, &e->d_hap, &e->d_hapoff, &e->d_hapdense, &e->d_place};
   for (DevBuf *b : all) b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->evb0) (void)hipEventDestroy(e->evb0);
@@ -513,6 +523,8 @@ void lancet_engine_destroy(lancet_engine *e) {
   if (e->ev_svc) (void)hipEventDestroy(e->ev_svc);
   if (e->ev_sup0) (void)hipEventDestroy(e->ev_sup0);      // (the haplotype capture's: around the support kernel)
   if (e->ev_sup1) (void)hipEventDestroy(e->ev_sup1);
+  if (e->ev_pl0) (void)hipEventDestroy(e->ev_pl0);        // (... and around the placement kernel)
+  if (e->ev_pl1) (void)hipEventDestroy(e->ev_pl1);
   if (e->stream3) (void)hipStreamDestroy(e->stream3);
   if (e->stream2) (void)hipStreamDestroy(e->stream2);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -546,6 +558,7 @@ int lancet_engine_set_haplotypes(lancet_engine *e, uint32_t words_per_window) {
   if (words_per_window && words_per_window < LC_HAP_MIN_WORDS) {
     e->err = "set_haplotypes: a window's buffer holds at least one header and one word of bases (" + std::to_string(LC_HAP_MIN_WORDS) + " words)"; return LANCET_E_ARG; }
   if (words_per_window >= HP_TRUNC) { e->err = "set_haplotypes: words_per_window is below 2^31"; return LANCET_E_ARG; }
+  if (e->hap_place && !lc_place_words_ok(words_per_window)) { e->err = "set_haplotypes: with the read placements on, a window's buffer holds at most 2^24 - 1 entries"; return LANCET_E_ARG; }
   e->hap_words = words_per_window;
   return LANCET_OK;
 }
@@ -583,6 +596,25 @@ int lancet_engine_set_haplotype_support(lancet_engine *e, int on, int max_mismat
     HIPCHK(e, hipEventCreate(&e->ev_sup1));
   }
   e->hap_sup = (uint32_t)on; e->hap_mm = (uint32_t)max_mismatches;
+  return LANCET_OK;
+}
+
+// ... and, per read, where it lies on the haplotype it fits best: a second kernel at the same point (hap_place.h), records in a buffer of
+// their own.  Same rules; the limit is this switch's own.  The record's index and offset fields bound the buffer and the longest path.
+int lancet_engine_set_haplotype_placements(lancet_engine *e, int on, int max_mismatches) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotype_placements while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotype_placements between an upload and its run"; return LANCET_E_STATE; }
+  if (on != 0 && on != 1) { e->err = "set_haplotype_placements: on is 0 or 1"; return LANCET_E_ARG; }
+  if (max_mismatches < 0 || max_mismatches > 255) { e->err = "set_haplotype_placements: max_mismatches is 0 .. 255"; return LANCET_E_ARG; }
+  if (on && !lc_place_words_ok(e->hap_words)) { e->err = "set_haplotype_placements: a window's buffer holds at most 2^24 - 1 entries (words_per_window above 9 * (2^24 - 1))"; return LANCET_E_ARG; }
+  if (on && !lc_place_params_ok(&e->params)) { e->err = "set_haplotype_placements: max_indel_len allows paths of 2^17 bases or more"; return LANCET_E_ARG; }
+  if (on && !e->ev_pl0) {
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipEventCreate(&e->ev_pl0));
+    HIPCHK(e, hipEventCreate(&e->ev_pl1));
+  }
+  e->hap_place = (uint32_t)on; e->place_mm = (uint32_t)max_mismatches;
   return LANCET_OK;
 }
 
@@ -664,6 +696,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   e->caps.hap_cov = e->caps2.hap_cov = e->hap_words ? e->hap_cov : 0u;
   e->caps.hap_sup = e->caps2.hap_sup = e->hap_words ? e->hap_sup : 0u;
   e->hap_mm_run = e->hap_mm;
+  e->hap_place_run = e->hap_words ? e->hap_place : 0u; e->place_mm_run = e->place_mm; e->place_meta = false;
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
   e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
@@ -911,7 +944,9 @@ static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatc
     ENS(e->d_hap, sizeof(uint32_t) * (size_t)nw * e->caps.hap_cap);
     if (nw) HIPCHK(e, hipMemsetAsync(e->d_haplen.p, 0, sizeof(uint32_t) * (size_t)nw, e->stream));
     o.hap_len = (LC_GLOBAL uint32_t *)e->d_haplen.p; o.hap_out = (LC_GLOBAL uint32_t *)e->d_hap.p;
+    if (e->hap_place_run) ENS(e->d_place, sizeof(uint32_t) * PL_WORDS * (size_t)e->n_reads);      // the reads' placement records (zeroed per run, in the wait)
   }
+  e->h_db = db;
   e->svc_cap = 0;
   e->pred.clear(); e->is_pred.assign(nw, 0);
   if (!e->debug_stop && !e->no_fat && !e->no_early_rerun) {
@@ -1302,6 +1337,7 @@ int lancet_engine_submit(lancet_engine *e) {
   e->variants.clear(); e->blob.clear(); e->stats.clear(); e->evt_len.clear(); e->evt.clear(); e->variants_lr.clear(); e->bx_blob.clear();
   e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
   e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear(); e->hap.cov_off.assign(1, 0u); e->hap.cov.clear(); e->hap.sup.clear(); e->ms_sup = 0;
+  e->place.p.clear(); e->place.tlen.clear(); e->place.read_begin.assign(1, 0u); e->ms_place = 0;
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1505,6 +1541,28 @@ int lancet_engine_wait(lancet_engine *e) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipEventElapsedTime(&e->ms_sup, e->ev_sup0, e->ev_sup1));
   }
+  // ---- ... and where each read lies on the haplotype it fits best: one record per read, in a buffer of its own, brought over in one copy
+  // (read_begin and rinfo, which give a record its class and the read's trimmed length, come over once per upload)
+  if (e->caps.hap_cap && e->hap_place_run) {
+    const size_t R = (size_t)e->n_reads, nw = (size_t)e->n_windows;
+    if (R) HIPCHK(e, hipMemsetAsync(e->d_place.p, 0, sizeof(uint32_t) * PL_WORDS * R, e->stream));
+    HIPCHK(e, hipEventRecord(e->ev_pl0, e->stream));
+    hipLaunchKernelGGL(hap_placement_kernel, dim3((unsigned)e->n_windows), dim3(LC_SUP_WG), 0, e->stream, (const DevBatch *)e->d_batch.p, (const uint32_t *)e->d_haplen.p,
+                       (const uint32_t *)e->d_hap.p, e->caps.hap_cap, e->place_mm_run, (uint32_t *)e->d_place.p, e->n_windows);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->ev_pl1, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipEventElapsedTime(&e->ms_place, e->ev_pl0, e->ev_pl1));
+    if (!e->place_meta) {
+      e->place_rb.resize(nw + 1); e->place_ri.resize(R);
+      HIPCHK(e, lc_copy(e, e->place_rb.data(), (const void *)e->h_db.read_begin, sizeof(uint32_t) * (nw + 1), hipMemcpyDeviceToHost));
+      if (R) HIPCHK(e, lc_copy(e, e->place_ri.data(), (const void *)e->h_db.rinfo, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+      e->place_meta = true;
+    }
+    e->place_rec.resize(PL_WORDS * R);
+    if (R) HIPCHK(e, lc_copy(e, e->place_rec.data(), e->d_place.p, sizeof(uint32_t) * PL_WORDS * R, hipMemcpyDeviceToHost));
+    lc_place_collect(e->n_windows, e->place_rb.data(), e->place_ri.data(), e->place_rec.data(), e->stats.data(), &e->place);
+  }
   if (e->caps.hap_cap) { const int rc = lc_read_haplotypes(e); if (rc) return rc; }
   e->ran = true;
   return LANCET_OK;
@@ -1578,6 +1636,19 @@ int lancet_engine_results_haplotype_support(lancet_engine *e, const uint32_t **s
   if (support) *support = (e->hap.sup.size() == (size_t)HP_SUP_WORDS * e->hap.h.size() && !e->hap.sup.empty()) ? e->hap.sup.data() : nullptr;
   return LANCET_OK;
 }
+int lancet_engine_results_haplotype_placements(lancet_engine *e, const lancet_read_placement **p, uint32_t *n_reads, const uint32_t **read_begin, const uint16_t **tlen) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  const bool have = !e->place.p.empty();
+  if (e->place.read_begin.empty()) e->place.read_begin.assign(1, 0u);
+  if (p) *p = have ? e->place.p.data() : nullptr;
+  if (n_reads) *n_reads = (uint32_t)e->place.p.size();
+  if (read_begin) *read_begin = e->place.read_begin.data();
+  if (tlen) *tlen = have ? e->place.tlen.data() : nullptr;
+  return LANCET_OK;
+}
+// HIP-event milliseconds of the placement kernel in the last run; 0 with the switch off
+float lancet_engine_haplotype_placement_ms(const lancet_engine *e) { return e ? e->ms_place : 0.f; }
 // HIP-event milliseconds of the support kernel in the last run; 0 with the switch off
 float lancet_engine_haplotype_support_ms(const lancet_engine *e) { return e ? e->ms_sup : 0.f; }
 // milliseconds the last run's read-back of the haplotypes took on the host clock (lengths, compaction, copy, parsing); 0 with the capture off

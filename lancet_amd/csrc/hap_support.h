@@ -47,15 +47,18 @@ DEV uint32_t sup_wave_min(uint32_t v, bool *lead) {
 DEV uint32_t sup_wave_min(uint32_t v, bool *lead) { *lead = true; return v; }      // (lanes one after the other: each brings its own)
 #endif
 
-// mm(o): read positions [lo, hi) lie on the path
-DEV uint32_t sup_mm(LC_GLOBAL const uint32_t *rw, int t, LC_GLOBAL const uint32_t *pw, int M, int o) {
+// mm(o): read positions [lo, hi) lie on the path.  The rule is stated here once, for this kernel and for the placement kernel (hap_place.h).
+// PAD: pw is a copy of the path words with a zero word in front and one behind (pw[-1], pw[npw]) -- every q below lies in -1 .. npw - 1 (the
+// first word's p is >= -15, the last word's p <= M - 1), so the two words are taken without the bounds tests.
+template <bool PAD, class PW>
+DEV uint32_t sup_mm_at(LC_GLOBAL const uint32_t *rw, int t, PW pw, int M, int o) {
   const int lo = o < 0 ? -o : 0, hi = t < M - o ? t : M - o;
   const int npw = (M + 15) >> 4;
   uint32_t mm = 0;
   for (int wi = lo >> 4; wi < ((hi + 15) >> 4); ++wi) {
     const int p = o + 16 * wi;                                   // path position under the word's first base (negative: in front of the path)
     const int q = p >> 4, s = p & 15;
-    const uint32_t a = (q >= 0 && q < npw) ? pw[q] : 0u, b = (q + 1 >= 0 && q + 1 < npw) ? pw[q + 1] : 0u;
+    const uint32_t a = PAD ? pw[q] : ((q >= 0 && q < npw) ? pw[q] : 0u), b = PAD ? pw[q + 1] : ((q + 1 >= 0 && q + 1 < npw) ? pw[q + 1] : 0u);
     const uint32_t at = (uint32_t)(((((unsigned long long)b) << 32) | (unsigned long long)a) >> (2 * s));
     uint32_t x = rw[wi] ^ at;
     x = (x | (x >> 1)) & 0x55555555u;                             // one bit per base that differs
@@ -65,6 +68,7 @@ DEV uint32_t sup_mm(LC_GLOBAL const uint32_t *rw, int t, LC_GLOBAL const uint32_
   }
   return mm;
 }
+DEV uint32_t sup_mm(LC_GLOBAL const uint32_t *rw, int t, LC_GLOBAL const uint32_t *pw, int M, int o) { return sup_mm_at<false>(rw, t, pw, M, o); }
 
 // A whole entry at word `at` of a window's buffer of which `used` words count: its length, group, where its support words are and where
 // the next entry starts.  false: no (further) whole entry -- the bounds lc_hap_collect (host_common.h) checks.

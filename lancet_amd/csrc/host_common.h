@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "layout.h"
 #include "../../include/lancet_engine.h"
@@ -240,6 +241,75 @@ static inline void lc_hap_collect(int n_windows, const uint32_t *len_word, const
       at += HP_HDR + nw + nc + nv + ns;
     }
   }
+}
+// ---- read placements (layout.h PL_*): the placement kernel's records as lancet_engine_results_haplotype_placements returns them.
+// Limits lancet_engine_set_haplotype_placements checks: entries a window's buffer may hold against the index field, the longest path
+// against the offset field.
+static inline bool lc_place_words_ok(uint32_t words_per_window) { return words_per_window / LC_HAP_MIN_WORDS <= PL_IDX_MAX; }
+static inline bool lc_place_params_ok(const lancet_params *p) { return p->max_indel_len >= 0 && (int64_t)LC_MAXW + p->max_indel_len + 256 < (int64_t)PL_OFF_BIAS; }
+struct LcPlaceResult { std::vector<lancet_read_placement> p; std::vector<uint32_t> read_begin; std::vector<uint16_t> tlen; };
+// read_begin: [n_windows + 1]; rinfo: [reads] DevBatch::rinfo; rec: [reads * PL_WORDS] as the kernel left them.  A window without a result
+// (status < 0) has no placed read, whatever its buffer held.
+static inline void lc_place_collect(int n_windows, const uint32_t *read_begin, const uint32_t *rinfo, const uint32_t *rec, const lancet_window_stats *stats, LcPlaceResult *r) {
+  const int nw = n_windows > 0 ? n_windows : 0;
+  const uint32_t R = nw ? read_begin[nw] : 0u;
+  lancet_read_placement none; memset(&none, 0, sizeof(none)); none.haplotype = -1;
+  r->p.assign((size_t)R, none); r->read_begin.assign(read_begin, read_begin + (nw ? nw + 1 : 0)); r->tlen.resize((size_t)R);
+  if (!nw) r->read_begin.assign(1, 0u);
+  for (uint32_t i = 0; i < R; ++i) r->tlen[i] = (uint16_t)RI_TLEN(rinfo[i]);
+  for (int w = 0; w < nw; ++w) {
+    if (stats[w].status < 0) continue;
+    for (uint32_t i = read_begin[w]; i < read_begin[w + 1]; ++i) {
+      const uint32_t w0 = rec[PL_WORDS * (size_t)i], w1 = rec[PL_WORDS * (size_t)i + 1];
+      if (!(w0 & PL_IDX_MAX)) continue;
+      lancet_read_placement &x = r->p[i];
+      x.haplotype = (int32_t)(w0 & PL_IDX_MAX) - 1;
+      x.mismatches = (uint16_t)(w0 >> PL_MM_SHIFT);
+      x.offset = (int32_t)((w1 & PL_OFF_MASK) << (32 - PL_OFF_BITS)) >> (32 - PL_OFF_BITS);      // (two's complement in PL_OFF_BITS bits)
+      x.n_offsets = (uint16_t)((w1 >> PL_NOFF_SHIFT) & PL_CNT_MAX);
+      x.n_haplotypes = (uint16_t)((w1 >> PL_NHAP_SHIFT) & PL_CNT_MAX);
+      x.cls = (uint16_t)((RI_NML(rinfo[i]) ? 2u : 0u) + (RI_REV(rinfo[i]) ? 1u : 0u));
+    }
+  }
+}
+
+// The alignment of a placed read on the window reference, through its haplotype's alignment: the one statement of the rule, for lancet_gpu
+// and the tests (lancet_amd/abi.py read_cigar restates it in Python, written apart from this).
+//   o, t: the placement's offset and the read's trimmed length; M, ref_off, cig[ncig]: the entry's length, stretch offset and CIGAR words
+//   (length << 4 | HP_OP_*; none: the path lies on its stretch base for base).
+// Read bases in front of path position 0 or behind M - 1 are S.  Over the path positions [max(0, o), min(M, o + t)) the entry's runs are
+// walked: columns of = and X become M (the read may differ from the path), I stays I, D stays D unless no kept column lies in front of it or
+// behind it.  *start: 0-based on the window reference, the stretch offset plus the reference columns in front of the first kept column.
+// Neighbouring equal ops merge.  out: length << 4 | BAM op (LC_RC_*).  Returns false for a read without an M -- one that lies wholly inside
+// an I run: *start is then the column behind the run.
+enum { LC_RC_M = 0, LC_RC_I = 1, LC_RC_D = 2, LC_RC_S = 4 };
+static inline bool lc_read_cigar(int32_t o, uint32_t t, uint32_t M, uint32_t ref_off, const uint32_t *cig, uint32_t ncig, uint32_t *start, std::vector<uint32_t> *out) {
+  out->clear();
+  const int64_t a = o > 0 ? o : 0, b = std::min<int64_t>((int64_t)M, (int64_t)o + (int64_t)t);
+  auto push = [&](uint32_t n, uint32_t op) { if (!n) return; if (!out->empty() && (out->back() & 15u) == op) out->back() += n << 4; else out->push_back(n << 4 | op); };
+  const uint32_t whole = M << 4 | (uint32_t)HP_OP_EQ;
+  if (!ncig) { cig = &whole; ncig = 1; }
+  *start = ref_off;
+  if (b <= a) { push(t, LC_RC_S); return false; }       // (no placement: nothing of the read lies on the path)
+  push((uint32_t)(a - (int64_t)o), LC_RC_S);
+  int64_t pp = 0, rc = 0, pend_d = 0;          // path position and stretch column in front of the run at hand; a D run waiting for a kept column behind it
+  bool kept = false, has_m = false;
+  for (uint32_t q = 0; q < ncig && pp < b; ++q) {
+    const int64_t L = (int64_t)(cig[q] >> 4); const uint32_t op = cig[q] & 15u;
+    if (op == (uint32_t)HP_OP_D) { if (kept) pend_d += L; rc += L; continue; }
+    const int64_t x0 = std::max(pp, a), x1 = std::min(pp + L, b);
+    if (x1 > x0) {
+      const bool m = op != (uint32_t)HP_OP_I;
+      if (!kept) { *start = ref_off + (uint32_t)(rc + (m ? x0 - pp : 0)); kept = true; }
+      if (pend_d) { push((uint32_t)pend_d, LC_RC_D); pend_d = 0; }
+      push((uint32_t)(x1 - x0), m ? LC_RC_M : LC_RC_I);
+      has_m = has_m || m;
+    }
+    pp += L; if (op != (uint32_t)HP_OP_I) rc += L;
+  }
+  if (!kept) *start = ref_off + (uint32_t)rc;
+  push((uint32_t)((int64_t)o + (int64_t)t - b), LC_RC_S);
+  return has_m;
 }
 static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const lancet_params *p, uint32_t evt_cap,
                                            uint32_t max_nodes_limit, int tier = 2) {

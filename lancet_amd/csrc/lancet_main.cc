@@ -44,7 +44,14 @@
 // that fit it alone among the paths of its (k, component) (alone_tf ... alone_nr), within --haplotype-support-mismatches N (default 5, the
 // reference's HD_DISTANCE_CUTOFF) mismatches of an ungapped placement; the first line names the columns.  Alone or with the other three; the
 // same rules; the buffer is 8 words per path larger.  With --haplotype-sam every SAM record gains the tags sf and sa (B:I, four values each).
+// --haplotype-reads FILE: SAM again, the same header, one record per PLACED read of every window (lancet_engine_set_haplotype_placements, within
+// --haplotype-read-mismatches N, default 5): the read realigned through the haplotype it fits best.  QNAME = chr:start-end|r=<the read's number
+// in its window> (the batch carries name ranks, not names), FLAG 16 for a reverse-strand read, POS / CIGAR from lc_read_cigar (host_common.h)
+// with the coordinate arithmetic of --haplotype-sam, MAPQ 255, SEQ the trimmed read, QUAL *, tags wn:Z hi:i (the pi of --haplotype-sam) kk:i
+// cp:i ho:i hm:i on:i hn:i sm:A (T / N).  A read selected by several overlapping windows gets a record per window.  Alone or with the other
+// four; the same rules; with --device-select the batches go the host route (SEQ comes from the host's packed words).
 #include "../../include/lancet_host.h"
+#include "host_common.h"      // lc_read_cigar
 #include "../../include/lancet_gather.h"
 
 #include <signal.h>
@@ -76,7 +83,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"haplotype-support", 0, 1}, {"haplotype-support-mismatches", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"haplotype-support", 0, 1}, {"haplotype-support-mismatches", 0, 1}, {"haplotype-reads", 0, 1}, {"haplotype-read-mismatches", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -158,6 +165,9 @@ void usage() {
         "                                       component, by class (fit_tf fit_tr fit_nf fit_nr alone_tf ...); alone or with the other three, same rules;\n"
         "                                       adds the tags sf sa to --haplotype-sam\n"
         "   --haplotype-support-mismatches <n>: mismatches an ungapped placement of a read on a path may have, 0 .. 255 [default: 5]\n"
+        "   --haplotype-reads <file>          : SAM, one record per read that fits a haplotype: the read realigned through the path it fits best (tags hi ho\n"
+        "                                       hm on hn: path, offset, mismatches, offsets and paths that are as good); alone or with the other four\n"
+        "   --haplotype-read-mismatches <n>   : mismatches such a read may have on its path, 0 .. 255 [default: 5]\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -172,8 +182,8 @@ int main(int argc, char **argv) {
   int max_indel_len = 500, max_mismatch = 2, max_unit_length = 4, min_report_unit = 3, min_report_len = 7, dist_from_str = 1;
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
-  std::string rendezvous, hap_file, sam_file, cov_file, sup_file;
-  int sup_mm = 5;
+  std::string rendezvous, hap_file, sam_file, cov_file, sup_file, reads_file;
+  int sup_mm = 5, reads_mm = 5;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -205,6 +215,7 @@ int main(int argc, char **argv) {
     else if (L == "active-region-off") ho.active_region = 0; else if (L == "verbose") verbose = 1; else if (L == "more-verbose") { verbose = 1; more_verbose = 1; } else if (L == "device") device = atoi(v); else if (L == "devices") devices = v; else if (L == "batch-windows") batch_windows = atoi(v);
     else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v; else if (L == "haplotype-coverage") cov_file = v;
     else if (L == "haplotype-support") sup_file = v; else if (L == "haplotype-support-mismatches") sup_mm = atoi(v);
+    else if (L == "haplotype-reads") reads_file = v; else if (L == "haplotype-read-mismatches") reads_mm = atoi(v);
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -216,6 +227,8 @@ int main(int argc, char **argv) {
   if (!cov_file.empty() && ranks > 1) return die("--haplotype-coverage is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (!sup_file.empty() && ranks > 1) return die("--haplotype-support is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (sup_mm < 0 || sup_mm > 255) return die("--haplotype-support-mismatches must be 0 .. 255");
+  if (!reads_file.empty() && ranks > 1) return die("--haplotype-reads is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (reads_mm < 0 || reads_mm > 255) return die("--haplotype-read-mismatches must be 0 .. 255");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -321,30 +334,36 @@ int main(int argc, char **argv) {
   }
   FILE *hap_out = nullptr;
   if (!hap_file.empty() && !(hap_out = fopen(hap_file.c_str(), "w"))) return die("cannot write " + hap_file);
-  FILE *sam_out = nullptr;
-  if (!sam_file.empty()) {
+  FILE *sam_out = nullptr, *reads_out = nullptr;
+  for (int q = 0; q < 2; ++q) {                          // --haplotype-sam and --haplotype-reads: one header
+    const std::string &file = q == 0 ? sam_file : reads_file;
+    if (file.empty()) continue;
     std::vector<std::pair<std::string, long>> contigs;
     if (!fasta_contigs(ref, &contigs)) return die("cannot read " + ref);
-    if (!(sam_out = fopen(sam_file.c_str(), "w"))) return die("cannot write " + sam_file);
-    fputs("@HD\tVN:1.6\tSO:unsorted\n", sam_out);
-    for (const auto &ct : contigs) fprintf(sam_out, "@SQ\tSN:%s\tLN:%ld\n", ct.first.c_str(), ct.second);
-    fputs("@PG\tID:lancet_gpu\tPN:lancet_gpu\n", sam_out);
+    FILE *f = fopen(file.c_str(), "w");
+    if (!f) return die("cannot write " + file);
+    fputs("@HD\tVN:1.6\tSO:unsorted\n", f);
+    for (const auto &ct : contigs) fprintf(f, "@SQ\tSN:%s\tLN:%ld\n", ct.first.c_str(), ct.second);
+    fputs("@PG\tID:lancet_gpu\tPN:lancet_gpu\n", f);
+    (q == 0 ? sam_out : reads_out) = f;
   }
   FILE *cov_out = nullptr;
   if (!cov_file.empty() && !(cov_out = fopen(cov_file.c_str(), "w"))) return die("cannot write " + cov_file);
   FILE *sup_out = nullptr;
   if (!sup_file.empty() && !(sup_out = fopen(sup_file.c_str(), "w"))) return die("cannot write " + sup_file);
   if (sup_out) fputs("#haplotype\tfit_tf\tfit_tr\tfit_nf\tfit_nr\talone_tf\talone_tr\talone_nf\talone_nr\n", sup_out);
-  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr, sup_on = sup_out != nullptr;
-  const bool aln_on = sam_on || cov_on;                  // the table is laid out by the alignment's columns
+  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr, sup_on = sup_out != nullptr, reads_on = reads_out != nullptr;
+  const bool aln_on = sam_on || cov_on || reads_on;      // the table is laid out by the alignment's columns; a read's CIGAR goes through its path's
   const bool hap_on = hap_out != nullptr || aln_on || sup_on;      // any of the files turns the capture on; the SAM and the coverage one the alignments as well
   auto hap_extra_for = [&](uint32_t longest) -> uint32_t { return (aln_on ? hap_cigar_words() : 0u) + (cov_on ? hap_cov_words(longest, max_indel_len) : 0u) + (sup_on ? hap_sup_words() : 0u); };
+  long n_hap_reads = 0;                            // --haplotype-reads: records written
   long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
-  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::string hapsup; /* --haplotype-support: its lines */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::string hapsup; /* --haplotype-support: its lines */ std::string hapreads; /* --haplotype-reads: its SAM records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
-                std::vector<std::string> raw; /* -V: Ref_t::rawseq of the batch's window w (the level-2 events refer to it by offset) */ };
+                std::vector<std::string> raw; /* -V: Ref_t::rawseq of the batch's window w (the level-2 events refer to it by offset) */
+                std::vector<uint32_t> rd_woff, rd_bases; /* --haplotype-reads: where read r of the batch starts in the packed words, and those words */ };
   std::vector<Job> jobs((size_t)nchunks);
   std::vector<Slot> slots(engs.size());
   for (size_t k = 0; k < engs.size(); ++k) { slots[k].e = engs[k]; slots[k].kept.resize((size_t)step); }
@@ -400,6 +419,39 @@ int main(int argc, char **argv) {
       const uint32_t *sup = nullptr;
       if (sup_on && lancet_engine_results_haplotype_support(sl.e, &sup) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
+      if (reads_on) {
+        // the reads' records: each placed read through its haplotype's CIGAR (lc_read_cigar), with --haplotype-sam's coordinates
+        const lancet_read_placement *pl = nullptr; uint32_t npl = 0; const uint32_t *prb = nullptr; const uint16_t *ptl = nullptr;
+        if (lancet_engine_results_haplotype_placements(sl.e, &pl, &npl, &prb, &ptl) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+        std::vector<uint32_t> first((size_t)sl.nk + 1, nh);       // haplotype i of window w is hp[first[w] + i]
+        for (uint32_t i = nh; i-- > 0;) if (hp[i].window >= 0 && hp[i].window < sl.nk) first[(size_t)hp[i].window] = i;
+        std::vector<uint32_t> ops; std::string seq; char head[320];
+        for (int w = 0; pl && w < sl.nk; ++w) {
+          const int tw = sl.kept[(size_t)w];
+          const char *hdr = lancet_host_window_hdr(H, tw);
+          int32_t start = 0, end = 0; lancet_host_window_span(H, tw, &start, &end);
+          for (uint32_t r = prb[w]; r < prb[w + 1] && r < npl && r < sl.rd_woff.size(); ++r) {
+            const lancet_read_placement &x = pl[r];
+            if (x.haplotype < 0) continue;
+            const uint32_t hi = first[(size_t)w] + (uint32_t)x.haplotype;
+            if (hi >= nh || hp[hi].window != w || hp[hi].index_in_window != x.haplotype || cig_off[hi + 1] > ncig) continue;
+            const lancet_haplotype &h = hp[hi];
+            uint32_t start0 = 0;
+            (void)lc_read_cigar(x.offset, ptl[r], h.len, h.ref_off, cig + cig_off[hi], cig_off[hi + 1] - cig_off[hi], &start0, &ops);
+            const uint32_t *rw = sl.rd_bases.data() + sl.rd_woff[r];
+            seq.assign((size_t)ptl[r], 'A');
+            for (uint32_t b = 0; b < ptl[r]; ++b) seq[b] = "ACGT"[(rw[b / 16u] >> (2u * (b % 16u))) & 3u];
+            snprintf(head, sizeof head, "%s|r=%u\t%d\t%s\t%ld\t255\t", hdr, r - prb[w], (x.cls & 1u) ? 16 : 0, chr_names[lancet_host_window_chrom(H, tw)], (long)start + (long)start0);
+            j.hapreads += head;
+            for (uint32_t op : ops) { j.hapreads += std::to_string(op >> 4); j.hapreads += (op & 15u) == LC_RC_M ? 'M' : (op & 15u) == LC_RC_I ? 'I' : (op & 15u) == LC_RC_D ? 'D' : 'S'; }
+            j.hapreads += "\t*\t0\t0\t"; j.hapreads += seq;
+            snprintf(head, sizeof head, "\t*\twn:Z:%s\thi:i:%d\tkk:i:%u\tcp:i:%u\tho:i:%d\thm:i:%u\ton:i:%u\thn:i:%u\tsm:A:%c\n", hdr, x.haplotype, (unsigned)h.kmer, (unsigned)h.component,
+                     x.offset, (unsigned)x.mismatches, (unsigned)x.n_offsets, (unsigned)x.n_haplotypes, (x.cls & 2u) ? 'N' : 'T');
+            j.hapreads += head;
+            ++n_hap_reads;
+          }
+        }
+      }
       for (uint32_t i = 0; i < nh; ++i) {
         const lancet_haplotype &x = hp[i];
         if (x.window < 0 || x.window >= sl.nk || (uint64_t)x.word_off + (x.len + 15u) / 16u > nwords) continue;
@@ -491,6 +543,7 @@ int main(int argc, char **argv) {
       if (!j.trace.empty()) fputs(j.trace.c_str(), stderr);
       if (!j.hapfa.empty() && fwrite(j.hapfa.data(), 1, j.hapfa.size(), hap_out) != j.hapfa.size()) { fail = "cannot write " + hap_file; return false; }
       if (!j.hapsam.empty() && fwrite(j.hapsam.data(), 1, j.hapsam.size(), sam_out) != j.hapsam.size()) { fail = "cannot write " + sam_file; return false; }
+      if (!j.hapreads.empty() && fwrite(j.hapreads.data(), 1, j.hapreads.size(), reads_out) != j.hapreads.size()) { fail = "cannot write " + reads_file; return false; }
       if (!j.hapsup.empty() && fwrite(j.hapsup.data(), 1, j.hapsup.size(), sup_out) != j.hapsup.size()) { fail = "cannot write " + sup_file; return false; }
       if (!j.hapcov.empty() && fwrite(j.hapcov.data(), 1, j.hapcov.size(), cov_out) != j.hapcov.size()) { fail = "cannot write " + cov_file; return false; }
       int arc = LANCET_OK;
@@ -555,6 +608,7 @@ int main(int argc, char **argv) {
     if (device_select) {
       std::string why;
       if (ho.linked) why = "linked reads";
+      else if (reads_on) why = "haplotype reads";          // (--haplotype-reads decodes SEQ from the host's packed words: the batch is assembled on the host)
       else if (!packed) why = "ASCII hand-over";
       else {
         lancet_window_slice SL;
@@ -600,8 +654,27 @@ int main(int argc, char **argv) {
       for (int32_t w = 0; w < nk; ++w) longest = std::max(longest, B.ref_off[w + 1] - B.ref_off[w]);
       if (cov_on && !more_verbose) { sl.raw.assign((size_t)nk, std::string()); for (int32_t w = 0; w < nk; ++w) sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
       if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
-          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK || lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK)
+          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK || lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK ||
+          lancet_engine_set_haplotype_placements(sl.e, reads_on ? 1 : 0, reads_mm) != LANCET_OK)
         return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
+    }
+    if (!taken && reads_on) {                                    // the batch's packed reads stay with the slot until its records are written
+      const uint32_t R = B.read_begin[nk];
+      sl.rd_woff.assign((size_t)R, 0u); sl.rd_bases.clear();
+      if (packed) {
+        const uint32_t n = PK.read_index ? PK.n_distinct : R;
+        sl.rd_bases.assign(PK.bases, PK.bases + PK.base_woff[n]);
+        for (uint32_t r = 0; r < R; ++r) sl.rd_woff[r] = PK.base_woff[PK.read_index ? PK.read_index[r] : r];
+      } else {
+        std::vector<uint32_t> good;
+        for (uint32_t r = 0; r < R; ++r) {
+          const uint32_t o = B.seq_off[r], len = B.seq_off[r + 1] - o; uint32_t ri = 0;
+          sl.rd_woff[r] = (uint32_t)sl.rd_bases.size();
+          sl.rd_bases.resize(sl.rd_bases.size() + (len + 15u) / 16u + 1u, 0u); good.assign((size_t)(len + 31u) / 32u + 1u, 0u);
+          lancet_pack_read(&P, B.seq + o, B.qual + o, (int)len, B.label[r], B.strand[r], B.mate[r], B.mapped[r], &ri, sl.rd_bases.data() + sl.rd_woff[r], good.data());
+        }
+      }
+      sl.rd_bases.push_back(0u);
     }
     if (!taken && (packed ? lancet_engine_upload_packed(sl.e, &B, &PK) : lancet_engine_upload(sl.e, &B)) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     t_engine += now() - t0;
@@ -648,8 +721,12 @@ int main(int argc, char **argv) {
       if (fclose(sup_out) != 0) return die("cannot write " + sup_file);
       fprintf(stderr, "[lancet_gpu] %ld haplotypes written to %s\n", n_hap, sup_file.c_str());
     }
+    if (reads_on) {
+      if (fclose(reads_out) != 0) return die("cannot write " + reads_file);
+      fprintf(stderr, "[lancet_gpu] %ld reads written to %s\n", n_hap_reads, reads_file.c_str());
+    }
     if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
-                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_on ? cov_file.c_str() : sup_file.c_str());
+                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_on ? cov_file.c_str() : sup_on ? sup_file.c_str() : reads_file.c_str());
   }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
@@ -697,7 +774,8 @@ int main(int argc, char **argv) {
     if (strcmp(argv[i], "--date-line") == 0 || strcmp(argv[i], "--rank") == 0 || strcmp(argv[i], "--rendezvous") == 0) { ++i; continue; }     // (what names the run / the process, not the job)
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
     if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0 || strcmp(argv[i], "--haplotype-coverage") == 0 ||
-        strcmp(argv[i], "--haplotype-support") == 0 || strcmp(argv[i], "--haplotype-support-mismatches") == 0) { ++i; continue; }  // (a second output of the same run)
+        strcmp(argv[i], "--haplotype-support") == 0 || strcmp(argv[i], "--haplotype-support-mismatches") == 0 ||
+        strcmp(argv[i], "--haplotype-reads") == 0 || strcmp(argv[i], "--haplotype-read-mismatches") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

@@ -167,6 +167,26 @@ enum { HP_OP_I = 1,        /* column with '-' in the reference string           
        HP_OP_D = 2,        /* column with '-' in the path string                                       */
        HP_OP_EQ = 7, HP_OP_X = 8 };   /* both strings have a base: the same / another                  */
 
+/* ---- read placements (lancet_engine_set_haplotype_placements; hap_place.h): one record of two words per read of the batch, in batch
+ * read order, in a buffer of its own (not in the windows' buffers: no entry changes).  All 0: the read is not placed.
+ *   word 0   bits  0..23  index_in_window of the haplotype + 1 (PL_IDX_BITS: at most PL_IDX_MAX whole entries to a window; a window's
+ *                         buffer of more than PL_IDX_MAX * (HP_HDR + 1) words is refused where the switch is set)
+ *            bits 24..31  mismatches (the limit is 0 .. 255, a placed read has no more)
+ *   word 1   bits  0..17  offset, two's complement (PL_OFF_BITS: -131072 .. 131071 ; DESIGN.md section 9 derives why no placement lies outside)
+ *            bits 18..24  n_offsets, saturating at PL_CNT_MAX
+ *            bits 25..31  n_haplotypes, saturating at PL_CNT_MAX */
+#define PL_IDX_BITS 24
+#define PL_IDX_MAX ((1u << PL_IDX_BITS) - 1u)
+#define PL_MM_SHIFT 24
+#define PL_OFF_BITS 18
+#define PL_OFF_BIAS (1 << (PL_OFF_BITS - 1))      /* offset + bias is the unsigned form the kernel orders (mismatches, offset) pairs by */
+#define PL_OFF_MASK ((1u << PL_OFF_BITS) - 1u)
+#define PL_CNT_BITS 7
+#define PL_CNT_MAX ((1u << PL_CNT_BITS) - 1u)
+#define PL_NOFF_SHIFT PL_OFF_BITS
+#define PL_NHAP_SHIFT (PL_OFF_BITS + PL_CNT_BITS)
+#define PL_WORDS 2u
+
 /* device-resident batch (after upload + prep) */
 struct DevBatch {
   int32_t n_windows;

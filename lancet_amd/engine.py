@@ -84,6 +84,11 @@ def lib():
         L.lancet_engine_results_haplotype_support.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32))]
         L.lancet_engine_haplotype_support_ms.restype = C.c_float
         L.lancet_engine_haplotype_support_ms.argtypes = [C.c_void_p]
+        L.lancet_engine_set_haplotype_placements.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.lancet_engine_results_haplotype_placements.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetReadPlacement)), C.POINTER(C.c_uint32),
+                                                                 C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint16))]
+        L.lancet_engine_haplotype_placement_ms.restype = C.c_float
+        L.lancet_engine_haplotype_placement_ms.argtypes = [C.c_void_p]
         L.lancet_engine_haplotype_readback_ms.restype = C.c_float
         L.lancet_engine_haplotype_readback_ms.argtypes = [C.c_void_p]
         L.lancet_engine_set_trace_level.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
@@ -163,14 +168,16 @@ class DeviceReads:
 class Engine:
     def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1, haplotype_words: int = 0,
                  haplotype_alignments: bool = False, haplotype_coverage: bool = False, haplotype_support: bool = False,
-                 haplotype_support_mismatches: int = 5):
+                 haplotype_support_mismatches: int = 5, haplotype_placements: bool = False, haplotype_placement_mismatches: int = 5):
         """trace_words: 32-bit words of trace events kept per window (0: no trace).  trace_level 1: the reference's -v lines; 2: its -V
         (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level).
         haplotype_words: 32-bit words kept per window for its assembled haplotypes (0: none; lancet_engine_set_haplotypes, haplotypes()).
         haplotype_alignments: each of them with its CIGAR against its reference stretch, out of the same words (set_haplotype_alignments).
         haplotype_coverage: each of them with the reads' support of every base of path and stretch, out of the same words (set_haplotype_coverage).
         haplotype_support: each of them with the numbers of reads that fit it, and fit it alone among the haplotypes of its (k, component), within
-        haplotype_support_mismatches mismatches, by class Tf Tr Nf Nr; eight more words each (set_haplotype_support)."""
+        haplotype_support_mismatches mismatches, by class Tf Tr Nf Nr; eight more words each (set_haplotype_support).
+        haplotype_placements: per read of the batch the haplotype it fits best, where it lies on it and with how many mismatches, within
+        haplotype_placement_mismatches (set_haplotype_placements, placements()); no words of the windows' buffers."""
         self.L = lib()
         self.params = params or abi.default_params()
         h = C.c_void_p()
@@ -196,6 +203,27 @@ class Engine:
         self._hap_sup = False
         if haplotype_support:
             self.set_haplotype_support(True, haplotype_support_mismatches)
+
+        if haplotype_placements:
+            self.set_haplotype_placements(True, haplotype_placement_mismatches)
+
+    def set_haplotype_placements(self, on: bool, max_mismatches: int = 5) -> None:
+        """lancet_engine_set_haplotype_placements: for the uploads that follow; nothing while the capture is off.  EngineError between an
+        upload and its run, and for max_mismatches outside 0 .. 255."""
+        self._chk(self.L.lancet_engine_set_haplotype_placements(self.h, 1 if on else 0, int(max_mismatches)))
+
+    def placements(self):
+        """(records, read_begin, tlen) of the last run: a numpy structured array (abi.PLACEMENT_DTYPE: haplotype = index_in_window or -1,
+        offset, mismatches, n_offsets, n_haplotypes, cls 0..3 = Tf Tr Nf Nr) with one record per read in the batch's read order, window w's
+        at read_begin[w] .. read_begin[w + 1], and every read's trimmed length.  Empty with the switch off (include/lancet_engine.h)."""
+        pp, n, rb, tl = C.POINTER(abi.LancetReadPlacement)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint16)()
+        self._chk(self.L.lancet_engine_results_haplotype_placements(self.h, C.byref(pp), C.byref(n), C.byref(rb), C.byref(tl)))
+        nw = len(self.results()[1]) if n.value else 0            # (one statistics record per window of the run, whatever route uploaded it)
+        return abi.placements_to_py(pp, n.value, rb, nw, tl)
+
+    def haplotype_placement_ms(self) -> float:
+        """HIP-event milliseconds of the placement kernel in the last run (0 with the switch off)."""
+        return float(self.L.lancet_engine_haplotype_placement_ms(self.h))
 
     def set_haplotypes(self, words_per_window: int) -> None:
         """lancet_engine_set_haplotypes: for the uploads that follow (0: off).  EngineError between an upload and its run."""

@@ -1,10 +1,13 @@
-"""python tools/haplotype_cost.py [windows] [--alignments] [--coverage] [--support] -- cost of the haplotype capture on the bench batch (workload.make_scan_batch(32768, 30, 30, seed=22), the batch resident): wall time of
+"""python tools/haplotype_cost.py [windows] [--alignments] [--coverage] [--support] [--placements] -- cost of the haplotype capture on the bench batch (workload.make_scan_batch(32768, 30, 30, seed=22), the batch resident): wall time of
 lancet_engine_run per step with the capture off and on (lancet_gpu's size for the batch), the kernels' time, and the read-back.
 --alignments: also with every haplotype's CIGAR (lancet_engine_set_haplotype_alignments; lancet_gpu --haplotype-sam's size for the batch), and the CIGAR words per batch.
 --coverage: also with every base's coverages on top of the CIGARs (lancet_engine_set_haplotype_coverage; lancet_gpu --haplotype-coverage's size for the batch): the window kernel's own time,
 the read-back, the words per window that are used, the truncated windows; every haplotype's arrays are checked for their shape.
 --support: also with the reads that fit every haplotype (lancet_engine_set_haplotype_support; lancet_gpu --haplotype-support's size for the batch, 5 mismatches): the support kernel's
-HIP-event time (not one of the run's kernels: it runs in the wait), the window kernel with and without the switch, the read-back; the counts are checked for their invariants."""
+HIP-event time (not one of the run's kernels: it runs in the wait), the window kernel with and without the switch, the read-back; the counts are checked for their invariants.
+--placements: also with the reads' placements (lancet_engine_set_haplotype_placements; lancet_gpu --haplotype-reads' size for the batch, 5 mismatches) and, as the yardstick, the
+support run: the placement kernel's HIP-event time beside the support kernel's on the same batch, the records' bytes (8 per read; their read-back and decoding is what the
+`place` step's wall time has beyond the `aln` step's and the kernel), reads placed / not placed / with n_haplotypes > 1."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,8 +15,9 @@ import numpy as np
 from lancet_amd import abi, engine, workload
 import hap_cases as hc
 
-args = [a for a in sys.argv[1:] if a not in ("--alignments", "--coverage", "--support")]
-sup = "--support" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--alignments", "--coverage", "--support", "--placements")]
+plc = "--placements" in sys.argv[1:]
+sup = "--support" in sys.argv[1:] or plc
 aln = "--alignments" in sys.argv[1:]
 cov = "--coverage" in sys.argv[1:]
 n = int(args[0]) if args else 32768
@@ -23,27 +27,29 @@ words = hc.ample_words(batch, p)
 longest = max(int(batch.ref_off[w + 1] - batch.ref_off[w]) for w in range(batch.n_windows))
 cov_words = words + 32 * 64 + 32 * 2 * (2 * longest + int(p.max_indel_len) + 256)
 res = {}
-once = ([("off", 0, False, False, False), ("on", words, False, False, False)] + ([("aln", words + 32 * 64, True, False, False)] if aln or cov else []) + ([("cov", cov_words, True, True, False)] if cov else [])
-        + ([("sup", words + 32 * 8, False, False, True)] if sup else []))
-runs = once + [(l + "2", hw, al, cv, sp) for l, hw, al, cv, sp in once]
-for label, hw, al, cv, sp in runs:
-    eng = engine.Engine(p, haplotype_words=hw, haplotype_alignments=al, haplotype_coverage=cv, haplotype_support=sp, haplotype_support_mismatches=5)
+once = ([("off", 0, False, False, False, False), ("on", words, False, False, False, False)] + ([("aln", words + 32 * 64, True, False, False, False)] if aln or cov or plc else [])
+        + ([("cov", cov_words, True, True, False, False)] if cov else []) + ([("sup", words + 32 * 8, False, False, True, False)] if sup else [])
+        + ([("place", words + 32 * 64, True, False, False, True)] if plc else []))
+runs = once + [(l + "2", hw, al, cv, sp, pl) for l, hw, al, cv, sp, pl in once]
+for label, hw, al, cv, sp, pl in runs:
+    eng = engine.Engine(p, haplotype_words=hw, haplotype_alignments=al, haplotype_coverage=cv, haplotype_support=sp, haplotype_support_mismatches=5,
+                        haplotype_placements=pl, haplotype_placement_mismatches=5)
     eng.upload(batch)
     names = eng.kernel_names()
     wi = names.index("window_kernel") if "window_kernel" in names else None
-    wall, kern, rb, wk, sk = [], [], [], [], []
+    wall, kern, rb, wk, sk, pk = [], [], [], [], [], []
     for it in range(12):
         t = time.perf_counter(); eng.run(); wall.append(1000 * (time.perf_counter() - t))
         kern.append(eng.timing_ms()[0]); rb.append(eng.haplotype_readback_ms())
         wk.append(eng.kernel_times()[wi] if wi is not None else eng.timing_ms()[1])
-        sk.append(eng.haplotype_support_ms())
+        sk.append(eng.haplotype_support_ms()); pk.append(eng.haplotype_placement_ms())
     v, st = eng.results()
     haps, trunc = ([], []) if not hw else eng.haplotypes()
     res[label] = (v, st)
     med = lambda a: float(np.median(a[2:]))
     used = sum(hc.words_of(h) + len(h.get("cigar", ())) + (2 * (h["len"] + h["ref_len"]) if "cov" in h else 0) + (8 if "support" in h else 0) for h in haps)
     print(f"{label}: words/window {hw} wall ms/step median {med(wall):.2f} (min {min(wall[2:]):.2f} max {max(wall[2:]):.2f}) kernels ms {med(kern):.2f} window kernel ms {med(wk):.2f} "
-          f"support kernel ms {med(sk):.2f} read-back ms {med(rb):.2f} read-back bytes {4 * used} haplotypes {len(haps)} bases {sum(h['len'] for h in haps)} cigar words {sum(len(h.get('cigar', ())) for h in haps)} "
+          f"support kernel ms {med(sk):.2f} placement kernel ms {med(pk):.2f} read-back ms {med(rb):.2f} read-back bytes {4 * used} haplotypes {len(haps)} bases {sum(h['len'] for h in haps)} cigar words {sum(len(h.get('cigar', ())) for h in haps)} "
           f"used words/window {used / max(1, batch.n_windows):.1f} truncated windows {sum(trunc)} records {len(v)} "
           f"bad {sum(1 for s in st if s['status'] < 0)} rerun {eng.rerun_count()}", flush=True)
     if cv:
@@ -60,11 +66,17 @@ for label, hw, al, cv, sp in runs:
             print("support invariants ok on", len(haps), "haplotypes; reads that fit", sum(sum(h["support"]["fit"]) for h in haps), "alone", sum(sum(h["support"]["alone"]) for h in haps),
                   "of", batch.n_reads, "reads", flush=True)
         haps = hsc.strip_support(haps)
-    if hw and label in ("on", "aln", "cov", "sup"):
+    if pl:
+        recs, rbeg, tl = eng.placements()
+        placed = recs["haplotype"] >= 0
+        print(f"{label}: placement records {len(recs)} ({recs.nbytes // 2} bytes read back per run, 8 per read) placed {int(placed.sum())} not placed {int((~placed).sum())} "
+              f"with n_haplotypes > 1 {int((recs['n_haplotypes'] > 1).sum())} with n_offsets > 1 {int((recs['n_offsets'] > 1).sum())} mismatches 0 {int((placed & (recs['mismatches'] == 0)).sum())}", flush=True)
+        assert len(recs) == batch.n_reads and (recs["haplotype"][~placed] == -1).all() and (recs["mismatches"][placed] <= 5).all()
+    if hw and label in ("on", "aln", "cov", "sup", "place"):
         import hap_align_cases as hac
         hc.check_shape(batch, st, hac.strip_cigar(haps), trunc); hc.check_link(batch, v, st, haps, windows=[w for w in range(batch.n_windows) if not trunc[w]])
         print("link check ok on", batch.n_windows, "windows", flush=True)
-    if label in ("aln", "cov"):
+    if label in ("aln", "cov", "place"):
         hac.check_cigars(batch, haps, v)
         print("cigar check ok on", len(haps), "haplotypes", flush=True)
     eng.close()
