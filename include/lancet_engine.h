@@ -441,6 +441,60 @@ int   lancet_engine_set_haplotype_placements(lancet_engine *e, int on, int max_m
 int   lancet_engine_results_haplotype_placements(lancet_engine *e, const lancet_read_placement **p, uint32_t *n_reads,
                                                  const uint32_t **read_begin /* [n_windows + 1] */, const uint16_t **tlen);
 float lancet_engine_haplotype_placement_ms(const lancet_engine *e);
+/* ---- ... and, per allele, the reads that carry it, the reference allele or something else at its site ----
+ * lancet_engine_set_haplotype_evidence(e, events_per_window, max_mismatches): after the windows of the runs that follow are through, a
+ * third kernel of that kind writes one record per EVENT of every whole entry.  The reference has no such value; this is its definition, all
+ * in integers, in the terms of the two definitions above (the read as the kernels see it: trimmed, t bases, in BAM orientation; offsets o
+ * in [k - t, M - k]; mm(o); d(r, h); the GROUP of an entry: the run of whole entries with its (kmer, component), which share their stretch).
+ * Events.  An event of an entry h is a maximal run of neighbouring CIGAR words whose op is not '=' -- what the kernels' transcript walk
+ *   turns into one record.  It has four numbers: rb, the stretch bases in front of it; rs, the stretch bases it spans (its D and X
+ *   lengths); pb, the path bases in front of it; ps, the path bases it spans (its I and X lengths).  A LANCET_HAP_IS_REF entry has none, a
+ *   LANCET_HAP_UNALIGNED one has one per run of X.
+ * Carriers.  An event e' of another entry h' of the group TOUCHES e = (rb, rs, ps, bases) iff rb' <= rb + rs and rb' + rs' >= rb (closed
+ *   intervals: an insertion at either edge touches).  h' carries ALT iff exactly one of its events touches and that one has the same rb, rs
+ *   and ps and the same ps path bases; REF iff none touches; OTHER otherwise.  h itself carries ALT.
+ * Sites.  The site of e on h' is the path interval [left, right): lo = min(rb, the smallest rb' of a touching event), hi = max(rb + rs,
+ *   the largest rb' + rs' of one), shift = the sum of ps" - rs" over the events of h' that lie wholly in front of lo, left = lo + shift,
+ *   right = hi + shift + the sum of ps' - rs' over the touching events.  For an ALT carrier that is [pb', pb' + ps), for a REF carrier
+ *   the image of [rb, rb + rs).
+ * Reads.  Best(r) = the entries of the group whose d(r, h') is the group's smallest and <= max_mismatches: the entries r FITS in the
+ *   sense of lancet_engine_set_haplotype_support.  On such an entry o* is the smallest offset with mm(o*) = d, the placement kernel's
+ *   `offset`.  r is INFORMATIVE for e on h' iff left >= 1, right + 1 <= M, o* <= left - 1 and o* + t >= right + 1: one path base on
+ *   either side of the site lies under the read.  r counts ALT for e iff it is informative on at least one ALT carrier of Best(r) and on
+ *   no REF or OTHER carrier; REF iff on at least one REF carrier and on no ALT or OTHER carrier; OTHER iff it is informative anywhere
+ *   and counts neither; a read that is informative nowhere counts nothing.  Per event: alt, ref and other, each by class Tf Tr Nf Nr.
+ * Limits: base qualities are not looked at; placements are ungapped; rivals are the group's entries only (the same string at two k is
+ * judged twice, each time among the entries of its k); a window whose reference path was not assembled has no REF carrier, so its ref
+ * counts are 0; in a truncated window the candidates are its whole entries; an event at a path's first or last base has no flank and so
+ * no informative read.  In lr_mode reads are reads here, not barcodes.
+ * events_per_window: records kept per window, 0 = off; max_mismatches 0..255, independent of the other two limits (else LANCET_E_ARG, as
+ * is an events_per_window of 2^24 or more); the state rules are those of lancet_engine_set_haplotypes.  The switch needs the capture and
+ * lancet_engine_set_haplotype_alignments; without either it does nothing.  The records lie in a buffer of their own: no entry, record,
+ * statistic or trace word changes.  A window with more events keeps the first events_per_window, whole, and is marked.  The kernel keeps a
+ * group's entries and events in lists of LANCET_EVID_GROUP_ENTRIES and LANCET_EVID_GROUP_EVENTS; the events of a group beyond either come
+ * with LANCET_EVID_UNEVALUATED and all counts 0, never with partial counts.
+ * lancet_engine_results_haplotype_evidence: after a run, the events of haplotype i of lancet_engine_results_haplotypes are
+ * ev[event_off[i] .. event_off[i + 1]), in CIGAR order; marked[w] = 1 where window w had more events than were kept.  `variant` is the
+ * index in lancet_engine_results' records of the one the event emitted: the record of haplotype h with seq_in_window in [first_variant,
+ * first_variant + n_variants) and pos + 1 - ref_start[window] - ref_off == rb; -1 where there is none (its alt coverage was 0, or the
+ * walk ended in front of it).  ev is NULL and n_events 0 with the switch off.
+ * lancet_engine_haplotype_evidence_ms: HIP-event milliseconds of the kernel in the last run; _readback_ms: host-clock milliseconds of the
+ * read-back (the windows' counts, the gather of the kept records on the device, one copy, the join). */
+#define LANCET_EVID_UNEVALUATED 1u
+#define LANCET_EVID_GROUP_ENTRIES 32u
+#define LANCET_EVID_GROUP_EVENTS 64u
+typedef struct lancet_variant_evidence {
+  int32_t  haplotype;       /* index in lancet_engine_results_haplotypes */
+  int32_t  variant;         /* index in lancet_engine_results' records, -1: none */
+  uint32_t rb, rs, pb, ps;
+  uint32_t flags;           /* LANCET_EVID_UNEVALUATED ; other bits 0 */
+  uint32_t alt[4], ref[4], other[4];   /* Tf Tr Nf Nr */
+} lancet_variant_evidence;
+int   lancet_engine_set_haplotype_evidence(lancet_engine *e, uint32_t events_per_window, int max_mismatches);   /* 0..255 */
+int   lancet_engine_results_haplotype_evidence(lancet_engine *e, const lancet_variant_evidence **ev, uint32_t *n_events,
+                                               const uint32_t **event_off /* [n_haplotypes + 1] */, const uint8_t **marked /* [n_windows] */);
+float lancet_engine_haplotype_evidence_ms(const lancet_engine *e);
+float lancet_engine_haplotype_evidence_readback_ms(const lancet_engine *e);
 
 /* The kernels one run launches, back to back on the engine's stream: lancet_engine_kernel_name(i) for i = 0, 1, ... (NULL past
  * the last) and the HIP-event duration of each in the last run (milliseconds; returns how many were written, <= cap). */

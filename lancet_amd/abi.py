@@ -179,6 +179,38 @@ def read_cigar(o: int, t: int, length: int, ref_off: int, cigar) -> tuple:
     return ref_off + kept[0][2], [(n, op) for n, op in ops if n], any(c[0] == "M" for c in kept)
 
 
+class LancetVariantEvidence(C.Structure):
+    """lancet_variant_evidence: one event of a haplotype with the reads for and against its allele (lancet_engine_results_haplotype_evidence)."""
+    _fields_ = [("haplotype", C.c_int32), ("variant", C.c_int32), ("rb", C.c_uint32), ("rs", C.c_uint32), ("pb", C.c_uint32), ("ps", C.c_uint32),
+                ("flags", C.c_uint32), ("alt", C.c_uint32 * 4), ("ref", C.c_uint32 * 4), ("other", C.c_uint32 * 4)]
+
+
+EVID_UNEVALUATED = 1          # LANCET_EVID_UNEVALUATED: the event's group is beyond the kernel's lists, all its counts are 0
+EVID_GROUP_ENTRIES, EVID_GROUP_EVENTS = 32, 64      # LANCET_EVID_GROUP_ENTRIES / _EVENTS
+
+
+def evidence_to_py(evptr, n: int, event_off, n_haplotypes: int) -> List[list]:
+    """Per haplotype the list of its events' dicts: rb rs pb ps variant flags alt ref other (the three: [Tf, Tr, Nf, Nr]); `variant` is the
+    index in the run's records, -1 without one.  No records (a NULL pointer): an empty list each."""
+    out = []
+    for i in range(n_haplotypes):
+        a, b = (int(event_off[i]), int(event_off[i + 1])) if evptr and n else (0, 0)
+        out.append([dict(rb=int(x.rb), rs=int(x.rs), pb=int(x.pb), ps=int(x.ps), variant=int(x.variant), flags=int(x.flags),
+                         alt=list(x.alt), ref=list(x.ref), other=list(x.other)) for x in (evptr[j] for j in range(a, b))])
+    return out
+
+
+def evidence_variant(h: dict, rb: int, ref_start: int, variants: Sequence[dict]) -> int:
+    """The index in `variants` (variants_to_py's dicts of one run) of the record the event at `rb` of haplotype h (haplotypes_to_py's dict)
+    emitted, -1 without one -- the rule of lc_evid_join (lancet_amd/csrc/host_common.h), restated: a transcript opens at the event's first
+    column, its position is the 1-based window start plus the stretch's offset plus the stretch bases in front, and a record holds that - 1."""
+    mine = range(h["first_variant"], h["first_variant"] + h["n_variants"])
+    for i, v in enumerate(variants):
+        if v["window"] == h["window"] and v["seq"] in mine and v["pos"] + 1 - ref_start - h["ref_off"] == rb:
+            return i
+    return -1
+
+
 def haplotypes_to_py(hptr, n: int, words: np.ndarray) -> List[dict]:
     """lancet_haplotype records as dicts, `seq` = the path string (2 bits per base, first base in the low bits of a word)."""
     out = []

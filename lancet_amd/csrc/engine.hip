@@ -19,6 +19,7 @@
 #include "host_common.h"
 #include "hap_support.h"   // hap_support_kernel: the reads that fit each haplotype, counted after the batch's windows are through
 #include "hap_place.h"     // hap_placement_kernel: where each read lies on the haplotype it fits best, written at the same point
+#include "hap_evidence.h"  // hap_evidence_kernel: per allele the reads that carry it, the reference allele or something else, behind those two
 #include "select_host.h"
 
 // window_fat.hip
@@ -349,6 +350,14 @@ struct lancet_engine {
   bool place_meta = false;                        // ... and are here: place_rb, place_ri
   std::vector<uint32_t> place_rb, place_ri, place_rec;
   LcPlaceResult place;
+  uint32_t evid = 0, evid_run = 0;                // lancet_engine_set_haplotype_evidence: records kept per window from a kernel of its own (hap_evidence.h), within
+  uint32_t evid_mm = 0, evid_mm_run = 0;          // evid_mm mismatches (the _run pair: of the batch that is uploaded)
+  hipEvent_t ev_ev0 = nullptr, ev_ev1 = nullptr;  // around the evidence kernel (created with the switch)
+  float ms_evid = 0, ms_evid_rb = 0;              // (ms_evid_rb: the read-back, on the host clock)
+  DevBuf d_evid, d_evlen, d_evoff, d_evdense;     // [n_windows * evid_run * EV_WORDS] zeroed per run, [n_windows]; the read-back's offsets and gathered records
+  std::vector<int32_t> evid_refstart;             // DevBatch::ref_start, brought over once per upload (evid_meta)
+  bool evid_meta = false;
+  LcEvidResult evr;
   DevBuf d_haplen, d_hap, d_hapoff, d_hapdense;
   LcHapResult hap;
   float ms_hap = 0;
@@ -508,7 +517,7 @@ void lancet_engine_destroy(lancet_engine *e) {
   DevBuf *all[] = {&e->d_params, &e->d_batch, &e->d_caps, &e->d_out, &e->d_works, &e->d_chr, &e->d_refstart, &e->d_refoff, &e->d_refasc,
                    &e->d_refcodes, &e->d_readbegin, &e->d_seqoff, &e->d_seq, &e->d_qual, &e->d_label, &e->d_strand, &e->d_mate, &e->d_mapped,
                    &e->d_rinfo, &e->d_name, &e->d_bw, &e->d_gw, &e->d_bases, &e->d_good, &e->d_variants, &e->d_blob, &e->d_counters,
-                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum, &e->d_haplen, &e->d_hap, &e->d_hapoff, &e->d_hapdense, &e->d_place};
+                   &e->d_stats, &e->d_evtlen, &e->d_evt, &e->d_workmem, &e->d_phase, &e->d_caps2, &e->d_works2, &e->d_workmem2, &e->d_out2, &e->d_winlist, &e->d_skip, &e->dbg_mem, &e->dbg_caps, &e->dbg_work, &e->dbg_s, &e->dbg_t, &e->dbg_len, &e->d_bx, &e->d_hp, &e->d_varlr, &e->d_bxblob, &e->d_pre, &e->d_blscratch, &e->d_blphase, &e->d_order, &e->d_prepool, &e->d_blscratch_large, &e->d_biglist, &e->d_svc, &e->d_svcscratch, &e->d_stage, &e->d_selwin, &e->d_selsum, &e->d_haplen, &e->d_hap, &e->d_hapoff, &e->d_hapdense, &e->d_place, &e->d_evid, &e->d_evlen, &e->d_evoff, &e->d_evdense};
   for (DevBuf *b : all) b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->evb0) (void)hipEventDestroy(e->evb0);
@@ -525,6 +534,8 @@ void lancet_engine_destroy(lancet_engine *e) {
   if (e->ev_sup1) (void)hipEventDestroy(e->ev_sup1);
   if (e->ev_pl0) (void)hipEventDestroy(e->ev_pl0);        // (... and around the placement kernel)
   if (e->ev_pl1) (void)hipEventDestroy(e->ev_pl1);
+  if (e->ev_ev0) (void)hipEventDestroy(e->ev_ev0);        // (... and around the evidence kernel)
+  if (e->ev_ev1) (void)hipEventDestroy(e->ev_ev1);
   if (e->stream3) (void)hipStreamDestroy(e->stream3);
   if (e->stream2) (void)hipStreamDestroy(e->stream2);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -618,6 +629,25 @@ int lancet_engine_set_haplotype_placements(lancet_engine *e, int on, int max_mis
   return LANCET_OK;
 }
 
+// ... and, per event of every entry, the reads that carry its allele, the reference's or something else: a third kernel at the same point
+// (hap_evidence.h), records in a buffer of their own.  Same rules; the limit is this switch's own.  The kernel orders (mismatches, offset)
+// pairs as the placement kernel does, so the longest path is bounded as there.
+int lancet_engine_set_haplotype_evidence(lancet_engine *e, uint32_t events_per_window, int max_mismatches) {
+  if (!e) return LANCET_E_ARG;
+  if (e->submitted) { e->err = "set_haplotype_evidence while a batch is in flight"; return LANCET_E_STATE; }
+  if (e->uploaded && !e->ran) { e->err = "set_haplotype_evidence between an upload and its run"; return LANCET_E_STATE; }
+  if (events_per_window > LC_EVID_CAP_MAX) { e->err = "set_haplotype_evidence: events_per_window is below 2^24"; return LANCET_E_ARG; }
+  if (max_mismatches < 0 || max_mismatches > 255) { e->err = "set_haplotype_evidence: max_mismatches is 0 .. 255"; return LANCET_E_ARG; }
+  if (events_per_window && !lc_place_params_ok(&e->params)) { e->err = "set_haplotype_evidence: max_indel_len allows paths of 2^17 bases or more"; return LANCET_E_ARG; }
+  if (events_per_window && !e->ev_ev0) {
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipEventCreate(&e->ev_ev0));
+    HIPCHK(e, hipEventCreate(&e->ev_ev1));
+  }
+  e->evid = events_per_window; e->evid_mm = (uint32_t)max_mismatches;
+  return LANCET_OK;
+}
+
 static int up(lancet_engine *e, DevBuf &b, const void *src, size_t bytes) {
   if (b.ensure(bytes ? bytes : 1)) { e->err = "hipMalloc failed"; return LANCET_E_OOM; }
   if (bytes) HIPCHK(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
@@ -697,6 +727,7 @@ static void lc_upload_caps(lancet_engine *e, const LcBatchSizes &b) {
   e->caps.hap_sup = e->caps2.hap_sup = e->hap_words ? e->hap_sup : 0u;
   e->hap_mm_run = e->hap_mm;
   e->hap_place_run = e->hap_words ? e->hap_place : 0u; e->place_mm_run = e->place_mm; e->place_meta = false;
+  e->evid_run = (e->hap_words && e->hap_aln) ? e->evid : 0u; e->evid_mm_run = e->evid_mm; e->evid_meta = false;      // (events are runs of CIGAR words: none without them)
   // settled windows (layout.h EngineCaps::settle): not while anything is on that wants to see a reference-only window's graph
   e->caps.settle = e->caps2.settle = (!e->evt_cap && !e->hap_words && !e->params.lr_mode && !e->no_settle) ? (e->settle_chain_only ? 2u : 1u) : 0u;
 }
@@ -945,6 +976,7 @@ static int lc_upload_rest(lancet_engine *e, const LcBatchSizes &b, const DevBatc
     if (nw) HIPCHK(e, hipMemsetAsync(e->d_haplen.p, 0, sizeof(uint32_t) * (size_t)nw, e->stream));
     o.hap_len = (LC_GLOBAL uint32_t *)e->d_haplen.p; o.hap_out = (LC_GLOBAL uint32_t *)e->d_hap.p;
     if (e->hap_place_run) ENS(e->d_place, sizeof(uint32_t) * PL_WORDS * (size_t)e->n_reads);      // the reads' placement records (zeroed per run, in the wait)
+    if (e->evid_run) { ENS(e->d_evid, sizeof(uint32_t) * EV_WORDS * (size_t)nw * e->evid_run); ENS(e->d_evlen, sizeof(uint32_t) * (size_t)nw); }      // the events' records (likewise)
   }
   e->h_db = db;
   e->svc_cap = 0;
@@ -1338,6 +1370,7 @@ int lancet_engine_submit(lancet_engine *e) {
   e->hap.h.clear(); e->hap.words.clear(); e->hap.truncated.assign((size_t)std::max(0, e->n_windows), 0); e->ms_hap = 0;
   e->hap.cigar_off.assign(1, 0u); e->hap.cigar.clear(); e->hap.cov_off.assign(1, 0u); e->hap.cov.clear(); e->hap.sup.clear(); e->ms_sup = 0;
   e->place.p.clear(); e->place.tlen.clear(); e->place.read_begin.assign(1, 0u); e->ms_place = 0;
+  e->evr.ev.clear(); e->evr.event_off.assign(1, 0u); e->evr.marked.assign((size_t)std::max(0, e->n_windows), 0); e->ms_evid = 0; e->ms_evid_rb = 0;
   if (e->n_windows == 0) { e->submitted = true; return LANCET_OK; }
   // The copies that lay out the early re-run tier synchronise this engine's stream: they go first, so that the host thread is not held
   // until the other engine's kernels are through (the wait below is only enqueued, on the device).
@@ -1409,6 +1442,38 @@ static int lc_read_haplotypes(lancet_engine *e) {
   }
   lc_hap_collect(nw, len.data(), off.data(), dense.data(), e->stats.data(), &e->hap);
   e->ms_hap = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return LANCET_OK;
+}
+
+// Read-back of the variant evidence, as of the haplotypes: the windows' event counts, then only the records they kept, gathered by the same
+// kernel (a record is EV_WORDS words) and brought over in one copy; the reference starts, which the join needs, come over once per upload.
+static int lc_read_evidence(lancet_engine *e) {
+  const int nw = e->n_windows;
+  const uint32_t cap = e->evid_run;
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> len((size_t)nw), off((size_t)nw + 1, 0), woff((size_t)nw + 1, 0);
+  HIPCHK(e, lc_copy(e, len.data(), e->d_evlen.p, sizeof(uint32_t) * (size_t)nw, hipMemcpyDeviceToHost));
+  if (!e->evid_meta) {
+    e->evid_refstart.resize((size_t)nw);
+    HIPCHK(e, lc_copy(e, e->evid_refstart.data(), (const void *)e->h_db.ref_start, sizeof(int32_t) * (size_t)nw, hipMemcpyDeviceToHost));
+    e->evid_meta = true;
+  }
+  uint64_t total = 0;
+  for (int w = 0; w < nw; ++w) {
+    total += lc_evid_used(len[(size_t)w], cap, e->stats[(size_t)w].status);
+    if (total * EV_WORDS >= 0xFFFFFFFFull) { e->err = "haplotype evidence: more than 2^32 words in one batch"; return LANCET_E_OOM; }
+    off[(size_t)w + 1] = (uint32_t)total; woff[(size_t)w + 1] = (uint32_t)(total * EV_WORDS);
+  }
+  std::vector<uint32_t> dense((size_t)total * EV_WORDS + 1, 0);
+  if (total) {
+    if (e->d_evoff.ensure(sizeof(uint32_t) * ((size_t)nw + 1)) || e->d_evdense.ensure(sizeof(uint32_t) * EV_WORDS * (size_t)total)) { e->err = "hipMalloc failed (haplotype evidence)"; return LANCET_E_OOM; }
+    HIPCHK(e, hipMemcpyAsync(e->d_evoff.p, woff.data(), sizeof(uint32_t) * ((size_t)nw + 1), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(hap_compact_kernel, dim3((unsigned)nw), dim3(64), 0, e->stream, (const uint32_t *)e->d_evid.p, cap * EV_WORDS, (const uint32_t *)e->d_evoff.p, (uint32_t *)e->d_evdense.p, nw);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, lc_copy(e, dense.data(), e->d_evdense.p, sizeof(uint32_t) * EV_WORDS * (size_t)total, hipMemcpyDeviceToHost));
+  }
+  lc_evid_collect(nw, len.data(), off.data(), dense.data(), cap, e->stats.data(), e->evid_refstart.data(), e->hap.h, e->variants.data(), e->variants.size(), &e->evr);
+  e->ms_evid_rb = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return LANCET_OK;
 }
 
@@ -1563,7 +1628,22 @@ int lancet_engine_wait(lancet_engine *e) {
     if (R) HIPCHK(e, lc_copy(e, e->place_rec.data(), e->d_place.p, sizeof(uint32_t) * PL_WORDS * R, hipMemcpyDeviceToHost));
     lc_place_collect(e->n_windows, e->place_rb.data(), e->place_ri.data(), e->place_rec.data(), e->stats.data(), &e->place);
   }
+  // ---- ... and the reads for and against every allele: one record per event of every entry, in a buffer of its own (read back behind the
+  // haplotypes, whose order the records are returned in)
+  if (e->caps.hap_cap && e->evid_run) {
+    const size_t nw = (size_t)e->n_windows;
+    HIPCHK(e, hipMemsetAsync(e->d_evid.p, 0, sizeof(uint32_t) * EV_WORDS * nw * e->evid_run, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_evlen.p, 0, sizeof(uint32_t) * nw, e->stream));
+    HIPCHK(e, hipEventRecord(e->ev_ev0, e->stream));
+    hipLaunchKernelGGL(hap_evidence_kernel, dim3((unsigned)e->n_windows), dim3(LC_SUP_WG), 0, e->stream, (const DevBatch *)e->d_batch.p, (const uint32_t *)e->d_haplen.p,
+                       (const uint32_t *)e->d_hap.p, e->caps.hap_cap, e->evid_mm_run, (uint32_t *)e->d_evid.p, (uint32_t *)e->d_evlen.p, e->evid_run, e->n_windows);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->ev_ev1, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipEventElapsedTime(&e->ms_evid, e->ev_ev0, e->ev_ev1));
+  }
   if (e->caps.hap_cap) { const int rc = lc_read_haplotypes(e); if (rc) return rc; }
+  if (e->caps.hap_cap && e->evid_run) { const int rc = lc_read_evidence(e); if (rc) return rc; }
   e->ran = true;
   return LANCET_OK;
 }
@@ -1647,6 +1727,19 @@ int lancet_engine_results_haplotype_placements(lancet_engine *e, const lancet_re
   if (tlen) *tlen = have ? e->place.tlen.data() : nullptr;
   return LANCET_OK;
 }
+int lancet_engine_results_haplotype_evidence(lancet_engine *e, const lancet_variant_evidence **ev, uint32_t *n_events, const uint32_t **event_off, const uint8_t **marked) {
+  if (!e) return LANCET_E_ARG;
+  if (!e->ran) { e->err = "results before run"; return LANCET_E_STATE; }
+  if (e->evr.event_off.size() != e->hap.h.size() + 1) e->evr.event_off.assign(e->hap.h.size() + 1, 0u);      // (the switch off: every haplotype an empty slice)
+  if (ev) *ev = e->evr.ev.empty() ? nullptr : e->evr.ev.data();
+  if (n_events) *n_events = (uint32_t)e->evr.ev.size();
+  if (event_off) *event_off = e->evr.event_off.data();
+  if (marked) *marked = e->evr.marked.data();
+  return LANCET_OK;
+}
+// HIP-event milliseconds of the evidence kernel in the last run, and host-clock milliseconds of its read-back; 0 with the switch off
+float lancet_engine_haplotype_evidence_ms(const lancet_engine *e) { return e ? e->ms_evid : 0.f; }
+float lancet_engine_haplotype_evidence_readback_ms(const lancet_engine *e) { return e ? e->ms_evid_rb : 0.f; }
 // HIP-event milliseconds of the placement kernel in the last run; 0 with the switch off
 float lancet_engine_haplotype_placement_ms(const lancet_engine *e) { return e ? e->ms_place : 0.f; }
 // HIP-event milliseconds of the support kernel in the last run; 0 with the switch off

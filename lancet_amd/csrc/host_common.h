@@ -311,6 +311,48 @@ static inline bool lc_read_cigar(int32_t o, uint32_t t, uint32_t M, uint32_t ref
   push((uint32_t)((int64_t)o + (int64_t)t - b), LC_RC_S);
   return has_m;
 }
+// ---- variant evidence (layout.h EV_*): the evidence kernel's records as lancet_engine_results_haplotype_evidence returns them.
+#define LC_EVID_CAP_MAX ((1u << 24) - 1u)      /* events_per_window lancet_engine_set_haplotype_evidence accepts */
+struct LcEvidResult { std::vector<lancet_variant_evidence> ev; std::vector<uint32_t> event_off{0u}; std::vector<uint8_t> marked; };
+// Records of window w that are kept, from its event count: none for a window that reports no result (status < 0).
+static inline uint32_t lc_evid_used(uint32_t n_events, uint32_t cap, int32_t status) { return status < 0 ? 0u : (n_events < cap ? n_events : cap); }
+// The record an event of haplotype h emitted: the one statement of the rule, for the engine, lancet_gpu and the tests (lancet_amd/abi.py
+// evidence_variant restates it in Python, written apart from this).  The transcript walk (kernels.h walk_column) opens a transcript at the
+// event's first column with t.pos = pos_in_ref + ref_start + trim5 -- pos_in_ref the stretch bases in front of the column, the event's rb;
+// trim5 the stretch's offset, the haplotype's ref_off -- and the record's pos is t.pos - 1.  v[v0 .. v1): the window's records.
+static inline int32_t lc_evid_join(const lancet_haplotype &h, uint32_t rb, int32_t ref_start, const lancet_variant *v, size_t v0, size_t v1) {
+  for (size_t i = v0; i < v1; ++i) {
+    if (v[i].seq_in_window < h.first_variant || v[i].seq_in_window >= h.first_variant + h.n_variants) continue;
+    if ((int64_t)v[i].pos + 1 - (int64_t)ref_start - (int64_t)h.ref_off == (int64_t)rb) return (int32_t)i;
+  }
+  return -1;
+}
+// ev_len: [n_windows] the events every window has; dense: the kept records of the windows one behind the other (window w's start at record
+// off[w], off[w + 1] - off[w] == lc_evid_used of it); haps: lc_hap_collect's, of the same run; v[nv]: the run's records, ordered by
+// (window, seq_in_window); ref_start: [n_windows] DevBatch::ref_start.
+static inline void lc_evid_collect(int n_windows, const uint32_t *ev_len, const uint32_t *off, const uint32_t *dense, uint32_t cap, const lancet_window_stats *stats,
+                                   const int32_t *ref_start, const std::vector<lancet_haplotype> &haps, const lancet_variant *v, size_t nv, LcEvidResult *r) {
+  r->ev.clear(); r->event_off.assign(1, 0u); r->marked.assign((size_t)(n_windows > 0 ? n_windows : 0), 0);
+  for (int w = 0; w < n_windows; ++w) r->marked[(size_t)w] = (stats[w].status >= 0 && ev_len[w] > cap) ? 1 : 0;
+  int cur_w = -1; uint32_t c = 0, c_end = 0; size_t v0 = 0, v1 = 0;
+  for (size_t i = 0; i < haps.size(); ++i) {
+    const lancet_haplotype &h = haps[i];
+    if (h.window != cur_w) {
+      cur_w = h.window; c = off[cur_w]; c_end = off[cur_w + 1];
+      while (v0 < nv && v[v0].window < cur_w) ++v0;
+      v1 = v0; while (v1 < nv && v[v1].window == cur_w) ++v1;
+    }
+    for (; c < c_end && dense[(size_t)c * EV_WORDS + EV_W_IDX] == (uint32_t)h.index_in_window; ++c) {
+      const uint32_t *q = dense + (size_t)c * EV_WORDS;
+      lancet_variant_evidence x; memset(&x, 0, sizeof(x));
+      x.haplotype = (int32_t)i; x.rb = q[EV_W_RB]; x.rs = q[EV_W_RS]; x.pb = q[EV_W_PB]; x.ps = q[EV_W_PS]; x.flags = q[EV_W_FLAGS];
+      for (int j = 0; j < 4; ++j) { x.alt[j] = q[EV_W_CNT + j]; x.ref[j] = q[EV_W_CNT + 4 + j]; x.other[j] = q[EV_W_CNT + 8 + j]; }
+      x.variant = lc_evid_join(h, x.rb, ref_start[cur_w], v, v0, v1);
+      r->ev.push_back(x);
+    }
+    r->event_off.push_back((uint32_t)r->ev.size());
+  }
+}
 static inline EngineCaps lc_caps_for_batch(const lancet_window_batch *b, const lancet_params *p, uint32_t evt_cap,
                                            uint32_t max_nodes_limit, int tier = 2) {
   std::vector<uint32_t> wb; return lc_caps_for_sizes(lc_sizes_of_batch(b, &wb), p, evt_cap, max_nodes_limit, tier);

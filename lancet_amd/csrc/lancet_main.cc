@@ -50,6 +50,14 @@
 // with the coordinate arithmetic of --haplotype-sam, MAPQ 255, SEQ the trimmed read, QUAL *, tags wn:Z hi:i (the pi of --haplotype-sam) kk:i
 // cp:i ho:i hm:i on:i hn:i sm:A (T / N).  A read selected by several overlapping windows gets a record per window.  Alone or with the other
 // four; the same rules; with --device-select the batches go the host route (SEQ comes from the host's packed words).
+// --variant-evidence FILE: per record of the VCF's raw material, the reads for and against its allele by haplotype fit
+// (lancet_engine_set_haplotype_evidence, within --variant-evidence-mismatches N, default 5).  The first line names the columns; then one line
+// per event that has a record (lc_evid_join, host_common.h), in window processing order: window, chromosome, the record's position, code, ref
+// and alt strings as the record holds them, k, component, path index, and the twelve counts alt / ref / other by class Tf Tr Nf Nr.  The
+// capture and the alignments are turned on with it; EVID_EVENTS records are kept per window.  Alone or with the other five; the same rules:
+// same VCF bytes, left out of ##cmdline, refused with --ranks above 1, windows with more events and unevaluated events counted on stderr.
+// With --haplotype-sam every SAM record with events gains the tag ev:Z: its events as rb,rs,pb,ps,flags and the twelve counts, joined by ';'.
+// With --device-select the device route works unchanged: the kernel reads the resident batch, whichever route made it.
 #include "../../include/lancet_host.h"
 #include "host_common.h"      // lc_read_cigar
 #include "../../include/lancet_gather.h"
@@ -83,7 +91,7 @@ const Opt OPTS[] = {
   {"min-coverage-normal", 'z', 1}, {"max-coverage-normal", 'j', 1}, {"min-phred-fisher", 's', 1},
   {"min-phred-fisher-str", 'E', 1}, {"min-strand-bias", 'f', 1}, {"max-unit-length", 'U', 1}, {"min-report-unit", 'N', 1},
   {"min-report-len", 'Y', 1}, {"dist-from-str", 'D', 1}, {"linked-reads", 'J', 0}, {"kmer-recovery", 'R', 0}, {"primary-alignment-only", 'I', 0},
-  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"haplotype-support", 0, 1}, {"haplotype-support-mismatches", 0, 1}, {"haplotype-reads", 0, 1}, {"haplotype-read-mismatches", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
+  {"XA-tag-filter", 'O', 0}, {"active-region-off", 'W', 0}, {"verbose", 'v', 0}, {"more-verbose", 'V', 0}, {"device", 0, 1}, {"devices", 0, 1}, {"batch-windows", 0, 1}, {"date-line", 0, 1}, {"strict", 0, 0}, {"device-select", 0, 0}, {"haplotypes", 0, 1}, {"haplotype-sam", 0, 1}, {"haplotype-coverage", 0, 1}, {"haplotype-support", 0, 1}, {"haplotype-support-mismatches", 0, 1}, {"haplotype-reads", 0, 1}, {"haplotype-read-mismatches", 0, 1}, {"variant-evidence", 0, 1}, {"variant-evidence-mismatches", 0, 1}, {"ranks", 0, 1}, {"rank", 0, 1}, {"rendezvous", 0, 1}, {"help", 'h', 0},
 };
 // -V: trace words per window of a batch whose longest window reference has `longest` bases.  512 words for the stage lines; MV_PATHS paths of
 // up to longest + --max-indel-len + 256 bases (EngineCaps::path_cap), a byte per base plus the event and the padding; 16 words per reference
@@ -103,6 +111,8 @@ uint32_t hap_cigar_words() { return MV_PATHS * 64u; }
 uint32_t hap_cov_words(uint32_t longest, int max_indel_len) { return MV_PATHS * 2u * (2u * longest + (uint32_t)max_indel_len + 256u); }
 // --haplotype-support: eight words per path
 uint32_t hap_sup_words() { return MV_PATHS * 8u; }
+// --variant-evidence: records kept per window (MV_PATHS paths of four events each; a buffer of its own, 72 bytes per record)
+const uint32_t EVID_EVENTS = 128;
 // --haplotype-sam: (name, length) of the contigs of a FASTA file in its order -- from its .fai when there is one, else from the file itself
 bool fasta_contigs(const std::string &path, std::vector<std::pair<std::string, long>> *out) {
   out->clear();
@@ -168,6 +178,10 @@ void usage() {
         "   --haplotype-reads <file>          : SAM, one record per read that fits a haplotype: the read realigned through the path it fits best (tags hi ho\n"
         "                                       hm on hn: path, offset, mismatches, offsets and paths that are as good); alone or with the other four\n"
         "   --haplotype-read-mismatches <n>   : mismatches such a read may have on its path, 0 .. 255 [default: 5]\n"
+        "   --variant-evidence <file>         : per record the reads that carry its allele, the reference allele or something else at its site, judged by the\n"
+        "                                       haplotypes they fit (alt / ref / other by class Tf Tr Nf Nr); alone or with the other five, same rules;\n"
+        "                                       adds the tag ev to --haplotype-sam\n"
+        "   --variant-evidence-mismatches <n> : mismatches a read may have on the haplotypes it is judged by, 0 .. 255 [default: 5]\n"
         "   --ranks <n>                       : n processes, one per GPU; records gathered to rank 0 over RCCL, same VCF for every n\n"
         "   --rank <r> --rendezvous <path>    : this process is rank r of --ranks (a launcher starts the ranks; without --rank the\n"
         "                                       program starts them itself)\n"
@@ -183,7 +197,8 @@ int main(int argc, char **argv) {
   int device = 0, batch_windows = 8192, verbose = 0, more_verbose = 0, strict = 0, ranks = 0, rank = -1, kmer_recovery = 0;
   int device_select = (getenv("LANCET_DEVICE_SELECT") && atoi(getenv("LANCET_DEVICE_SELECT")) != 0) ? 1 : 0;
   std::string rendezvous, hap_file, sam_file, cov_file, sup_file, reads_file;
-  int sup_mm = 5, reads_mm = 5;
+  int sup_mm = 5, reads_mm = 5, evid_mm = 5;
+  std::string evid_file;
   double cov_ratio = 0.01;
   lancet_host_opts ho; lancet_host_opts_default(&ho);
   lancet_filters flt; lancet_filters_default(&flt);
@@ -216,6 +231,7 @@ int main(int argc, char **argv) {
     else if (L == "date-line") date_line = v; else if (L == "bed") bed = v; else if (L == "rg-file") rg_file = v; else if (L == "strict") strict = 1; else if (L == "device-select") device_select = 1; else if (L == "haplotypes") hap_file = v; else if (L == "haplotype-sam") sam_file = v; else if (L == "haplotype-coverage") cov_file = v;
     else if (L == "haplotype-support") sup_file = v; else if (L == "haplotype-support-mismatches") sup_mm = atoi(v);
     else if (L == "haplotype-reads") reads_file = v; else if (L == "haplotype-read-mismatches") reads_mm = atoi(v);
+    else if (L == "variant-evidence") evid_file = v; else if (L == "variant-evidence-mismatches") evid_mm = atoi(v);
     else if (L == "ranks") ranks = atoi(v); else if (L == "rank") rank = atoi(v); else if (L == "rendezvous") rendezvous = v;
     else if (L == "help") { usage(); return 0; }
   }
@@ -229,6 +245,8 @@ int main(int argc, char **argv) {
   if (sup_mm < 0 || sup_mm > 255) return die("--haplotype-support-mismatches must be 0 .. 255");
   if (!reads_file.empty() && ranks > 1) return die("--haplotype-reads is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
   if (reads_mm < 0 || reads_mm > 255) return die("--haplotype-read-mismatches must be 0 .. 255");
+  if (!evid_file.empty() && ranks > 1) return die("--variant-evidence is not offered together with --ranks above 1: the gather to rank 0 carries records only (--devices a,b works)");
+  if (evid_mm < 0 || evid_mm > 255) return die("--variant-evidence-mismatches must be 0 .. 255");
   if (ranks > 0 && rank < 0) {
     // the launcher: rank r = this program again with --rank r --rendezvous <path>; rank 0 writes the VCF to the stdout they all inherit
     if (rendezvous.empty()) {
@@ -352,13 +370,17 @@ int main(int argc, char **argv) {
   FILE *sup_out = nullptr;
   if (!sup_file.empty() && !(sup_out = fopen(sup_file.c_str(), "w"))) return die("cannot write " + sup_file);
   if (sup_out) fputs("#haplotype\tfit_tf\tfit_tr\tfit_nf\tfit_nr\talone_tf\talone_tr\talone_nf\talone_nr\n", sup_out);
-  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr, sup_on = sup_out != nullptr, reads_on = reads_out != nullptr;
-  const bool aln_on = sam_on || cov_on || reads_on;      // the table is laid out by the alignment's columns; a read's CIGAR goes through its path's
+  FILE *evid_out = nullptr;
+  if (!evid_file.empty() && !(evid_out = fopen(evid_file.c_str(), "w"))) return die("cannot write " + evid_file);
+  if (evid_out) fputs("#window\tchrom\tpos\tcode\tref\talt\tk\tcomponent\tpath\talt_Tf\talt_Tr\talt_Nf\talt_Nr\tref_Tf\tref_Tr\tref_Nf\tref_Nr\tother_Tf\tother_Tr\tother_Nf\tother_Nr\n", evid_out);
+  const bool sam_on = sam_out != nullptr, cov_on = cov_out != nullptr, sup_on = sup_out != nullptr, reads_on = reads_out != nullptr, evid_on = evid_out != nullptr;
+  const bool aln_on = sam_on || cov_on || reads_on || evid_on;      // the table is laid out by the alignment's columns; a read's CIGAR goes through its path's; events are runs of CIGAR words
+  long n_evid = 0, n_evid_marked = 0, n_evid_uneval = 0;          // --variant-evidence: lines written, windows with more events than EVID_EVENTS, events of groups beyond the kernel's lists
   const bool hap_on = hap_out != nullptr || aln_on || sup_on;      // any of the files turns the capture on; the SAM and the coverage one the alignments as well
   auto hap_extra_for = [&](uint32_t longest) -> uint32_t { return (aln_on ? hap_cigar_words() : 0u) + (cov_on ? hap_cov_words(longest, max_indel_len) : 0u) + (sup_on ? hap_sup_words() : 0u); };
   long n_hap_reads = 0;                            // --haplotype-reads: records written
   long n_hap = 0, n_hap_truncated = 0;             // --haplotypes: records written, windows whose haplotypes did not all fit hap_words_for
-  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::string hapsup; /* --haplotype-support: its lines */ std::string hapreads; /* --haplotype-reads: its SAM records */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
+  struct Job { bool have = false; std::string trace; std::string hapfa; /* --haplotypes: the batch's FASTA records */ std::string hapsam; /* --haplotype-sam: its SAM records */ std::string hapcov; /* --haplotype-coverage: its tables */ std::string hapsup; /* --haplotype-support: its lines */ std::string hapreads; /* --haplotype-reads: its SAM records */ std::string evid; /* --variant-evidence: its lines */ std::vector<lancet_variant> v; std::string blob; std::vector<lancet_variant_lr> lr; std::vector<uint32_t> bx; std::vector<std::string> bxn;
                std::vector<int64_t> widx; /* --ranks: tiled (= global) number of the batch's window w */ };
   std::vector<std::vector<uint8_t>> parts;      // --ranks: this rank's batches, packed (lancet_records_pack), in batch order
   struct Slot { lancet_engine *e = nullptr; std::future<int> fut; int chunk = -1; int nk = 0; long base = 0; std::vector<int32_t> kept; std::vector<std::string> bxn;
@@ -419,6 +441,12 @@ int main(int argc, char **argv) {
       const uint32_t *sup = nullptr;
       if (sup_on && lancet_engine_results_haplotype_support(sl.e, &sup) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
       for (int w = 0; w < sl.nk; ++w) if (trunc[w]) ++n_hap_truncated;
+      const lancet_variant_evidence *evd = nullptr; uint32_t nevd = 0; const uint32_t *ev_off = nullptr; const uint8_t *ev_marked = nullptr;
+      if (evid_on) {
+        if (lancet_engine_results_haplotype_evidence(sl.e, &evd, &nevd, &ev_off, &ev_marked) != LANCET_OK) { fail = std::string("engine: ") + lancet_engine_last_error(sl.e); return false; }
+        for (int w = 0; w < sl.nk; ++w) if (ev_marked[w]) ++n_evid_marked;
+        for (uint32_t q = 0; q < nevd; ++q) if (evd[q].flags & LANCET_EVID_UNEVALUATED) ++n_evid_uneval;
+      }
       if (reads_on) {
         // the reads' records: each placed read through its haplotype's CIGAR (lc_read_cigar), with --haplotype-sam's coordinates
         const lancet_read_placement *pl = nullptr; uint32_t npl = 0; const uint32_t *prb = nullptr; const uint16_t *ptl = nullptr;
@@ -461,6 +489,21 @@ int main(int argc, char **argv) {
         std::string seq((size_t)x.len, 'A');
         for (uint32_t b = 0; b < x.len; ++b) seq[b] = "ACGT"[(words[x.word_off + b / 16u] >> (2u * (b % 16u))) & 3u];
         // the haplotype's coverages: 4 per path base (an+ an- at+ at-), then 4 per base of the stretch (rn+ rn- rt+ rt-)
+        const uint32_t e0 = (evd && ev_off[i + 1] <= nevd) ? ev_off[i] : 0u, e1 = (evd && ev_off[i + 1] <= nevd) ? ev_off[i + 1] : 0u;      // the haplotype's events
+        for (uint32_t q = e0; q < e1; ++q) {
+          const lancet_variant_evidence &ev = evd[q];
+          if (ev.variant < 0 || (uint32_t)ev.variant >= nv) continue;
+          const lancet_variant &r = v[ev.variant];
+          j.evid += hdr; j.evid += '\t'; j.evid += chr_names[lancet_host_window_chrom(H, tw)]; j.evid += '\t'; j.evid += std::to_string(r.pos); j.evid += '\t'; j.evid += (char)r.code; j.evid += '\t';
+          j.evid.append(blob + r.ref_off, r.ref_len); j.evid += '\t'; j.evid.append(blob + r.alt_off, r.alt_len);
+          snprintf(head, sizeof head, "\t%u\t%u\t%d", (unsigned)x.kmer, (unsigned)x.component, x.index_in_window);
+          j.evid += head;
+          for (int c = 0; c < 4; ++c) { j.evid += '\t'; j.evid += std::to_string(ev.alt[c]); }
+          for (int c = 0; c < 4; ++c) { j.evid += '\t'; j.evid += std::to_string(ev.ref[c]); }
+          for (int c = 0; c < 4; ++c) { j.evid += '\t'; j.evid += std::to_string(ev.other[c]); }
+          j.evid += '\n';
+          ++n_evid;
+        }
         const uint16_t *pcv = nullptr, *rcv = nullptr;
         if (cov_on && cov_off[i + 1] <= ncov && cov_off[i + 1] - cov_off[i] == 4u * (x.len + x.ref_len)) { pcv = cov + cov_off[i]; rcv = pcv + 4u * (size_t)x.len; }
         if (hap_out) {
@@ -496,6 +539,13 @@ int main(int argc, char **argv) {
           if (sup) for (int q = 0; q < 2; ++q) {           // --haplotype-support as well: fit and alone, Tf Tr Nf Nr
             j.hapsam += q == 0 ? "\tsf:B:I" : "\tsa:B:I";
             for (int c = 0; c < 4; ++c) { j.hapsam += ','; j.hapsam += std::to_string(sup[8u * (size_t)i + 4u * (uint32_t)q + (uint32_t)c]); }
+          }
+          for (uint32_t q = e0; q < e1; ++q) {               // --variant-evidence as well: the events, rb,rs,pb,ps,flags and alt ref other by Tf Tr Nf Nr
+            const lancet_variant_evidence &ev = evd[q];
+            j.hapsam += q == e0 ? "\tev:Z:" : ";";
+            snprintf(head, sizeof head, "%u,%u,%u,%u,%u", ev.rb, ev.rs, ev.pb, ev.ps, ev.flags);
+            j.hapsam += head;
+            for (int c = 0; c < 12; ++c) { j.hapsam += ','; j.hapsam += std::to_string(c < 4 ? ev.alt[c] : c < 8 ? ev.ref[c - 4] : ev.other[c - 8]); }
           }
           j.hapsam += '\n';
         }
@@ -545,6 +595,7 @@ int main(int argc, char **argv) {
       if (!j.hapsam.empty() && fwrite(j.hapsam.data(), 1, j.hapsam.size(), sam_out) != j.hapsam.size()) { fail = "cannot write " + sam_file; return false; }
       if (!j.hapreads.empty() && fwrite(j.hapreads.data(), 1, j.hapreads.size(), reads_out) != j.hapreads.size()) { fail = "cannot write " + reads_file; return false; }
       if (!j.hapsup.empty() && fwrite(j.hapsup.data(), 1, j.hapsup.size(), sup_out) != j.hapsup.size()) { fail = "cannot write " + sup_file; return false; }
+      if (!j.evid.empty() && fwrite(j.evid.data(), 1, j.evid.size(), evid_out) != j.evid.size()) { fail = "cannot write " + evid_file; return false; }
       if (!j.hapcov.empty() && fwrite(j.hapcov.data(), 1, j.hapcov.size(), cov_out) != j.hapcov.size()) { fail = "cannot write " + cov_file; return false; }
       int arc = LANCET_OK;
       if (ranked) {                                  // the records travel: keyed, reduced, window numbers of the whole tiling
@@ -620,7 +671,8 @@ int main(int argc, char **argv) {
           if (more_verbose && lancet_engine_set_trace_level(sl.e, trace_words_for(longest, max_indel_len), 2) != LANCET_OK) return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
           if (hap_on && (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
                          lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK ||
-                         lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK))
+                         lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK ||
+                         lancet_engine_set_haplotype_evidence(sl.e, evid_on ? EVID_EVENTS : 0u, evid_mm) != LANCET_OK))
             return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
         }
         const int rc = lancet_engine_upload_windows(sl.e, dev_reads[dev], &SL, &ho, sl.kept.data(), &nk);
@@ -655,7 +707,8 @@ int main(int argc, char **argv) {
       if (cov_on && !more_verbose) { sl.raw.assign((size_t)nk, std::string()); for (int32_t w = 0; w < nk; ++w) sl.raw[(size_t)w].assign(B.ref_bases + B.ref_off[w], B.ref_bases + B.ref_off[w + 1]); }
       if (lancet_engine_set_haplotypes(sl.e, hap_words_for(longest, max_indel_len) + hap_extra_for(longest)) != LANCET_OK || lancet_engine_set_haplotype_alignments(sl.e, aln_on ? 1 : 0) != LANCET_OK ||
           lancet_engine_set_haplotype_coverage(sl.e, cov_on ? 1 : 0) != LANCET_OK || lancet_engine_set_haplotype_support(sl.e, sup_on ? 1 : 0, sup_mm) != LANCET_OK ||
-          lancet_engine_set_haplotype_placements(sl.e, reads_on ? 1 : 0, reads_mm) != LANCET_OK)
+          lancet_engine_set_haplotype_placements(sl.e, reads_on ? 1 : 0, reads_mm) != LANCET_OK ||
+          lancet_engine_set_haplotype_evidence(sl.e, evid_on ? EVID_EVENTS : 0u, evid_mm) != LANCET_OK)
         return die(std::string("engine: ") + lancet_engine_last_error(sl.e));
     }
     if (!taken && reads_on) {                                    // the batch's packed reads stay with the slot until its records are written
@@ -725,8 +778,14 @@ int main(int argc, char **argv) {
       if (fclose(reads_out) != 0) return die("cannot write " + reads_file);
       fprintf(stderr, "[lancet_gpu] %ld reads written to %s\n", n_hap_reads, reads_file.c_str());
     }
+    if (evid_on) {
+      if (fclose(evid_out) != 0) return die("cannot write " + evid_file);
+      fprintf(stderr, "[lancet_gpu] %ld events written to %s\n", n_evid, evid_file.c_str());
+      if (n_evid_marked || n_evid_uneval) fprintf(stderr, "lancet_gpu: %ld window(s) with more than %u events (the first ones are kept), %ld unevaluated event(s) of groups beyond %u paths or %u events: all their counts are 0\n",
+                                                  n_evid_marked, EVID_EVENTS, n_evid_uneval, (unsigned)LANCET_EVID_GROUP_ENTRIES, (unsigned)LANCET_EVID_GROUP_EVENTS);
+    }
     if (n_hap_truncated) fprintf(stderr, "lancet_gpu: %ld window(s) whose haplotypes did not all fit their buffer (%u paths of the longest window reference + --max-indel-len bases): the first ones are in %s\n",
-                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_on ? cov_file.c_str() : sup_on ? sup_file.c_str() : reads_file.c_str());
+                                 n_hap_truncated, MV_PATHS, hap_out ? hap_file.c_str() : sam_on ? sam_file.c_str() : cov_on ? cov_file.c_str() : sup_on ? sup_file.c_str() : reads_on ? reads_file.c_str() : evid_file.c_str());
   }
   for (auto &kv : dev_reads) lancet_device_reads_destroy(kv.second);
   double t_gather = 0;
@@ -775,7 +834,8 @@ int main(int argc, char **argv) {
     if (strcmp(argv[i], "--device-select") == 0) continue;       // (which route assembles the batches: the same VCF either way)
     if (strcmp(argv[i], "--haplotypes") == 0 || strcmp(argv[i], "--haplotype-sam") == 0 || strcmp(argv[i], "--haplotype-coverage") == 0 ||
         strcmp(argv[i], "--haplotype-support") == 0 || strcmp(argv[i], "--haplotype-support-mismatches") == 0 ||
-        strcmp(argv[i], "--haplotype-reads") == 0 || strcmp(argv[i], "--haplotype-read-mismatches") == 0) { ++i; continue; }  // (a second output of the same run)
+        strcmp(argv[i], "--haplotype-reads") == 0 || strcmp(argv[i], "--haplotype-read-mismatches") == 0 ||
+        strcmp(argv[i], "--variant-evidence") == 0 || strcmp(argv[i], "--variant-evidence-mismatches") == 0) { ++i; continue; }  // (a second output of the same run)
     cmdline += " "; cmdline += argv[i];
   }
   if (date_line.empty()) { time_t t = time(nullptr); date_line = ctime(&t); }

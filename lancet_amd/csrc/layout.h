@@ -187,6 +187,17 @@ enum { HP_OP_I = 1,        /* column with '-' in the reference string           
 #define PL_NHAP_SHIFT (PL_OFF_BITS + PL_CNT_BITS)
 #define PL_WORDS 2u
 
+/* ---- variant evidence (lancet_engine_set_haplotype_evidence; hap_evidence.h): records of EV_WORDS words, events_per_window of them per
+ * window, in a buffer of its own, in entry order and within an entry in event order; a word per window beside it counts the events the
+ * window has -- more than events_per_window: the first ones are kept, whole, and the window is marked.
+ *   word EV_W_IDX     index_in_window of the entry
+ *        EV_W_RB .. EV_W_PS   bases of the stretch in front of the event, bases of it the event spans, the same on the path
+ *        EV_W_FLAGS   LANCET_EVID_*
+ *        EV_W_CNT ..  EV_COUNTS counts: alt Tf Tr Nf Nr, ref Tf Tr Nf Nr, other Tf Tr Nf Nr */
+enum { EV_W_IDX = 0, EV_W_RB, EV_W_RS, EV_W_PB, EV_W_PS, EV_W_FLAGS, EV_W_CNT };
+#define EV_COUNTS 12u
+#define EV_WORDS (EV_W_CNT + EV_COUNTS)
+
 /* device-resident batch (after upload + prep) */
 struct DevBatch {
   int32_t n_windows;

@@ -89,6 +89,13 @@ def lib():
                                                                  C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint16))]
         L.lancet_engine_haplotype_placement_ms.restype = C.c_float
         L.lancet_engine_haplotype_placement_ms.argtypes = [C.c_void_p]
+        L.lancet_engine_set_haplotype_evidence.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+        L.lancet_engine_results_haplotype_evidence.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.LancetVariantEvidence)), C.POINTER(C.c_uint32),
+                                                               C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8))]
+        L.lancet_engine_haplotype_evidence_ms.restype = C.c_float
+        L.lancet_engine_haplotype_evidence_ms.argtypes = [C.c_void_p]
+        L.lancet_engine_haplotype_evidence_readback_ms.restype = C.c_float
+        L.lancet_engine_haplotype_evidence_readback_ms.argtypes = [C.c_void_p]
         L.lancet_engine_haplotype_readback_ms.restype = C.c_float
         L.lancet_engine_haplotype_readback_ms.argtypes = [C.c_void_p]
         L.lancet_engine_set_trace_level.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
@@ -168,7 +175,8 @@ class DeviceReads:
 class Engine:
     def __init__(self, params: Optional[abi.LancetParams] = None, device: int = 0, trace_words: int = 0, trace_level: int = 1, haplotype_words: int = 0,
                  haplotype_alignments: bool = False, haplotype_coverage: bool = False, haplotype_support: bool = False,
-                 haplotype_support_mismatches: int = 5, haplotype_placements: bool = False, haplotype_placement_mismatches: int = 5):
+                 haplotype_support_mismatches: int = 5, haplotype_placements: bool = False, haplotype_placement_mismatches: int = 5,
+                 haplotype_evidence: int = 0, haplotype_evidence_mismatches: int = 5):
         """trace_words: 32-bit words of trace events kept per window (0: no trace).  trace_level 1: the reference's -v lines; 2: its -V
         (--more-verbose) lines as well -- a diagnostics mode in which every graph takes the general build (lancet_engine_set_trace_level).
         haplotype_words: 32-bit words kept per window for its assembled haplotypes (0: none; lancet_engine_set_haplotypes, haplotypes()).
@@ -177,7 +185,10 @@ class Engine:
         haplotype_support: each of them with the numbers of reads that fit it, and fit it alone among the haplotypes of its (k, component), within
         haplotype_support_mismatches mismatches, by class Tf Tr Nf Nr; eight more words each (set_haplotype_support).
         haplotype_placements: per read of the batch the haplotype it fits best, where it lies on it and with how many mismatches, within
-        haplotype_placement_mismatches (set_haplotype_placements, placements()); no words of the windows' buffers."""
+        haplotype_placement_mismatches (set_haplotype_placements, placements()); no words of the windows' buffers.
+        haplotype_evidence: records kept per window for the events of its haplotypes -- per allele the reads that carry it, the reference allele
+        or something else at its site, within haplotype_evidence_mismatches (set_haplotype_evidence; needs haplotype_alignments; haplotypes()
+        then gives every dict its "events"); no words of the windows' buffers either."""
         self.L = lib()
         self.params = params or abi.default_params()
         h = C.c_void_p()
@@ -206,6 +217,30 @@ class Engine:
 
         if haplotype_placements:
             self.set_haplotype_placements(True, haplotype_placement_mismatches)
+
+        self._evid = 0
+        if haplotype_evidence:
+            self.set_haplotype_evidence(haplotype_evidence, haplotype_evidence_mismatches)
+
+    def set_haplotype_evidence(self, events_per_window: int, max_mismatches: int = 5) -> None:
+        """lancet_engine_set_haplotype_evidence: for the uploads that follow (0: off); nothing while the capture or its alignments are off.
+        EngineError between an upload and its run, and for max_mismatches outside 0 .. 255."""
+        self._chk(self.L.lancet_engine_set_haplotype_evidence(self.h, int(events_per_window), int(max_mismatches)))
+        self._evid = int(events_per_window)
+
+    def evidence_marked(self) -> list:
+        """Per window of the last run 1 where it had more events than haplotype_evidence records (the first ones are kept, whole)."""
+        ep, n, op, mp = C.POINTER(abi.LancetVariantEvidence)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        self._chk(self.L.lancet_engine_results_haplotype_evidence(self.h, C.byref(ep), C.byref(n), C.byref(op), C.byref(mp)))
+        nw = self._batch.n_windows if self._batch is not None else 0
+        return [int(mp[w]) for w in range(nw)]
+
+    def haplotype_evidence_ms(self) -> float:
+        """HIP-event milliseconds of the evidence kernel in the last run (0 with the switch off)."""
+        return float(self.L.lancet_engine_haplotype_evidence_ms(self.h))
+
+    def haplotype_evidence_readback_ms(self) -> float:
+        return float(self.L.lancet_engine_haplotype_evidence_readback_ms(self.h))
 
     def set_haplotype_placements(self, on: bool, max_mismatches: int = 5) -> None:
         """lancet_engine_set_haplotype_placements: for the uploads that follow; nothing while the capture is off.  EngineError between an
@@ -256,7 +291,10 @@ class Engine:
         haplotypes did not fit.  Both empty / all zero with the capture off.  With haplotype_alignments every dict also has "cigar": (length, op)
         pairs, op one of = X I D (I: bases the reference stretch does not have).  With haplotype_coverage every dict has "cov": {"path": len x 4
         uint16 (an+ an- at+ at-), "ref": ref_len x 4 uint16 (rn+ rn- rt+ rt-)}, the cells of the reference's vertical alignment.  With
-        haplotype_support every dict has "support": {"fit": [Tf, Tr, Nf, Nr], "alone": [Tf, Tr, Nf, Nr]}, the reads that fit it (include/lancet_engine.h)."""
+        haplotype_support every dict has "support": {"fit": [Tf, Tr, Nf, Nr], "alone": [Tf, Tr, Nf, Nr]}, the reads that fit it (include/lancet_engine.h).
+        With haplotype_evidence every dict has "events": its events in CIGAR order, each a dict rb rs pb ps variant flags alt ref other -- the
+        last three [Tf, Tr, Nf, Nr], `variant` the index in results()'s records of the one the event emitted or -1 (evidence_marked(): the
+        windows that had more events than were kept)."""
         hp, n, wp, nwd, tp = C.POINTER(abi.LancetHaplotype)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint8)()
         self._chk(self.L.lancet_engine_results_haplotypes(self.h, C.byref(hp), C.byref(n), C.byref(wp), C.byref(nwd), C.byref(tp)))
         words = np.ctypeslib.as_array(wp, shape=(nwd.value,)).copy() if nwd.value else np.zeros(0, np.uint32)
@@ -278,6 +316,11 @@ class Engine:
             self._chk(self.L.lancet_engine_results_haplotype_support(self.h, C.byref(sp)))
             for i, h in enumerate(haps):
                 h["support"] = abi.support_to_py(sp[8 * i:8 * i + 8] if sp else [0] * 8)
+        if self._evid:
+            ep, ne, op, mp = C.POINTER(abi.LancetVariantEvidence)(), C.c_uint32(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+            self._chk(self.L.lancet_engine_results_haplotype_evidence(self.h, C.byref(ep), C.byref(ne), C.byref(op), C.byref(mp)))
+            for h, evs in zip(haps, abi.evidence_to_py(ep, ne.value, op, len(haps))):
+                h["events"] = evs
         return haps, [int(tp[w]) for w in range(nw)]
 
     def haplotype_readback_ms(self) -> float:

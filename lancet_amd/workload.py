@@ -224,7 +224,7 @@ def kernel_fingerprint() -> str:
     import os
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     h = hashlib.sha1()
-    for f in ("build_lds.h", "build_lds_impl.h", "kernels.h", "hap_support.h", "hap_place.h", "layout.h", "wave.h", "engine.hip", "window_fat.hip"):
+    for f in ("build_lds.h", "build_lds_impl.h", "kernels.h", "hap_support.h", "hap_place.h", "hap_evidence.h", "layout.h", "wave.h", "engine.hip", "window_fat.hip"):
         h.update(f.encode())
         h.update(open(os.path.join(d, f), "rb").read())
     from . import build as _b
